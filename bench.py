@@ -15,15 +15,27 @@ resident in HBM.  With N GPUs the graph is replicated and start vertices are sha
 range: rank r walks batch k * N + r; no collective is on the walk path ("weak" scaling:
 per-GPU work per step is fixed).
 
-ONE JSON line on rank 0.  Beside the contract's keys:
+ONE JSON line on rank 0.  A plain run measures the headline alone: it builds the graph and the
+headline's tables, warms up, times the K steps and prints the contract's keys with
+  config        the workload
+  setup         one-off costs (graph build, trim, tables)
   roofline      the headline walk kernel: bytes / HIP-event duration against 8 TB/s
+--full adds every other leg (each still skipped by its --no-* option):
+  value_pipeline  p = q = 1: the same walks out in degree ranks (fit_streaming's launch)
+  gather_ceiling  in the rooflines: the memory ceilings of the tables, probed on this box (untimed)
   biased        the same graph walked exactly at p = 0.5, q = 2 (at p = q = 1 a step is two
-                gathers; the second-order bias is where the sampler works)
+                gathers; the second-order bias is where the sampler works), and other (p, q)
   fast_mode     fast mode at p = 0.5, q = 2 (same distribution, not the same draws)
+  reference_trim_cap, weighted, api
+                the graph trimmed at the reference's cap, the weighted cfg 2 graph, the API
+                surface end to end
   sgns          K launches of the SGNS kernel on a 10^8 x 128 model (embedding-updates/s)
   cpu_baseline  the CPU oracle (a port of the reference's algorithm) on this box's cores:
                 walks single-thread and all-core, SGNS single-thread and all-core
-  setup         one-off costs (graph build, trim, tables)
+  summary       a compact summary of every leg
+
+--dump-outputs DIR writes what the headline launch of the last timed step returned (rank 0):
+DIR/walks.npy and DIR/valid.npy, float64, the same fixed sample of rows in every run (seed 0).
 """
 import argparse
 import json
@@ -99,7 +111,17 @@ def parse(argv=None):
                     help="start the ranks through torch.distributed.run also at --gpus 1 (at --gpus N > 1 "
                          "this is what happens anyway when RANK is not in the environment)")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the spawned ranks (0 = a free one)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (ranked pipeline launch, memory ceilings, biased "
+                         "regimes, fast mode, reference cap, weighted graph, API, SGNS, CPU baseline); a plain run "
+                         "times the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the walks the headline's last timed step returned (a fixed, "
+                         "seeded sample of rows) as DIR/walks.npy and DIR/valid.npy, float64")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_command(argv, n, port):
@@ -178,6 +200,25 @@ def reference_algorithmic_bytes(torch, g, walks, valid, rows=65536):
     d = deg[w[:, :-1]]
     total = (16 + 8 * d + 4).sum() + (16 + 4 * d[:, :-1]).sum()
     return float(total) / float(d.numel())
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: at most this much of walks, float64
+
+
+def dump_outputs(directory, walks, valid):
+    """--dump-outputs: the walks and valid flags the headline launch returned, as float64 (exact for
+    int32 vertex ids); a launch larger than DUMP_BYTES is sampled by rows, the same rows for the same
+    shape in every run (seed 0), in row order."""
+    import numpy as np
+    import torch
+
+    rows, width = walks.shape
+    n = int(min(rows, max(1, DUMP_BYTES // (8 * (width + 1)))))
+    pick = np.sort(np.random.default_rng(0).choice(rows, n, replace=False)) if n < rows else np.arange(rows)
+    idx = torch.from_numpy(pick).to(walks.device)
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "walks.npy"), walks[idx].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(directory, "valid.npy"), valid[idx].cpu().numpy().astype(np.float64))
 
 
 class WalkLeg:
@@ -313,7 +354,8 @@ def main():
     # every launch of a walk kernel in this process has the bench's size: the rocprofv3
     # --kernel-trace average of the kernel is then the HIP-event average reported below
     prepare_tables(torch, g, p, q, "exact", setup, "headline")
-    if rank == 0 and (g.hops8 is not None or g.hops is not None):
+    full = args.full
+    if full and rank == 0 and (g.hops8 is not None or g.hops is not None):
         # the ceiling the walk kernel is compared with, observed on THIS box: random gathers of
         # the kernel's entry width over this graph's own hop table (untimed; before the K steps)
         table, width = (g.hops8, 8) if (g.hops8 is not None and p == 1.0 and q == 1.0) else (g.hops, 16)
@@ -327,7 +369,7 @@ def main():
     # That launch is the headline; the launch that writes vertex ids (what random_walk() puts in
     # its DataFrame: the hop-table kernel) is timed first and reported beside it.
     in_ranks = False
-    if p == 1.0 and q == 1.0 and g.unit_weights and not args.no_ranked:
+    if full and p == 1.0 and q == 1.0 and g.unit_weights and not args.no_ranked:
         t0 = time.perf_counter()
         g.build_ranked()
         torch.cuda.synchronize()
@@ -338,6 +380,8 @@ def main():
         leg = WalkLeg(torch, rw, g, start_all, W, L, p, q, "exact", batch, rank, world, audition=not args.no_audition)
         rv = leg.run(args.steps, args.warmup, barrier)
         ev, sv = reduce_job(torch, dist, use_dist, dev, rv["elapsed"], rv["steps_done"])
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, leg.walks, leg.valid)
         if rank == 0:
             vertex_leg = {"value": sv / ev, "unit": "walk-steps/s", "ms_per_step": 1e3 * ev / args.steps,
                           "what": "the same walks written as vertex ids (randomwalk.walk's default, the "
@@ -352,12 +396,15 @@ def main():
     res = leg.run(args.steps, args.warmup, barrier)
     elapsed, steps_total = reduce_job(torch, dist, use_dist, dev, res["elapsed"], res["steps_done"])
     value = steps_total / elapsed
+    if args.dump_outputs and rank == 0 and not in_ranks:
+        dump_outputs(args.dump_outputs, leg.walks, leg.valid)
     head_kernel = kernel_name(g, p, q)
     # the SGNS leg's vocabulary, built as fit_streaming builds it (pipeline.corpus_vocabulary: pass 1
     # over EVERY batch of the virtual corpus, descending token counts) -- untimed setup; the walks
     # are the headline's (ranks at p = q = 1), regenerated batch by batch into the leg's buffers
     sg_vocab = None
-    if not args.no_sgns:
+    run_sgns = full and not args.no_sgns
+    if run_sgns:
         from node2vec_amd.pipeline import corpus_vocabulary
 
         def count_walk(k):
@@ -378,7 +425,7 @@ def main():
     # one block of walks per SGNS launch, so that no launch trains rows the model has already seen
     # (a model that has seen its rows before skips more targets at |f| >= 6: measured 5 - 8 % faster)
     sg_blocks = max(1, min(args.steps + args.warmup, leg.batch // nv))
-    sg_walks = leg.walks[: nv * W * sg_blocks][leg.valid[: nv * W * sg_blocks].bool()].clone()
+    sg_walks = leg.walks[: nv * W * sg_blocks][leg.valid[: nv * W * sg_blocks].bool()].clone() if full else None
     ref_bytes = reference_algorithmic_bytes(torch, g, leg.walks, leg.valid)
     # (short: the driver's record keeps 120 characters of a string; the details are separate keys)
     workload = (f"{args.config} {cfg['gen']} {g.n_vertices} vertices / {g.n_edges} edges, p={p:g} q={q:g}, "
@@ -419,7 +466,7 @@ def main():
 
     # ---- the second-order bias on the same graph: exact mode and fast mode (layered or rejection sampler) -------------
     bp, bq = BIASED_PQ
-    if not args.no_biased and (bp, bq) != (p, q):
+    if full and not args.no_biased and (bp, bq) != (p, q):
         prepare_tables(torch, g, bp, bq, "exact", setup, "biased")
         leg = WalkLeg(torch, rw, g, start_all, W, L, bp, bq, "exact", cfg["biased_batch"], rank, world, audition=not args.no_audition)
         r2 = leg.run(args.steps, args.warmup, barrier)
@@ -448,7 +495,7 @@ def main():
     # the other arrangements of the three classes on the two stacks of the alias pairing, each
     # with its own closed form: "other" overfull (cfg 5's p, q), the return slot
     # sharing a stack with "other", the return slot alone overfull.  Same tables, same launches.
-    if not args.no_biased and not args.no_regimes:
+    if full and not args.no_biased and not args.no_regimes:
         regimes = []
         for rp, rq, what in ((4.0, 0.25, "other alone overfull"), (4.0, 2.0, "return + other underfull"),
                              (0.25, 0.5, "return + other overfull / return alone overfull"),
@@ -463,7 +510,7 @@ def main():
             torch.cuda.empty_cache()
         if rank == 0:
             out["biased_other_regimes"] = regimes
-    if not args.no_fast:
+    if full and not args.no_fast:
         prepare_tables(torch, g, bp, bq, "fast", setup, "fast")
         leg = WalkLeg(torch, rw, g, start_all, W, L, bp, bq, "fast", batch, rank, world, audition=not args.no_audition)
         r3 = leg.run(args.steps, args.warmup, barrier)
@@ -492,37 +539,37 @@ def main():
     # ---- the same graph trimmed at the REFERENCE's default cap (constants.py:6: 100 000; randomwalk.py:252-253)
     # instead of the examples' 10 000: rows of 65 536 slots and more (mixed wedge table), hub lists of thousands
     # of entries.  Two legs: p = q = 1 as fit_streaming launches it, and the exact biased kernel at (0.5, 2).
-    if not args.no_ref_cap and cfg["gen"] == "chung_lu" and setup["trim_cap"] not in (0, 100_000):
+    if full and not args.no_ref_cap and cfg["gen"] == "chung_lu" and setup["trim_cap"] not in (0, 100_000):
         out_cap = bench_reference_cap(args, cfg, torch, dist, rw, dev, W, L, rank, world, barrier, use_dist, setup)
         if rank == 0 and out_cap:
             out["reference_trim_cap"] = out_cap
 
     # ---- exact biased walks on a WEIGHTED graph (no closed form: every table of a step is different): the cfg 2
     # graph with fp32 weights U[0.1, 2], every start vertex x W walks in ONE call, step-synchronous kernels
-    if not args.no_weighted and world == 1:
+    if full and not args.no_weighted and world == 1:
         out_w = bench_weighted(args, torch, rw, dev, W, L)
         if rank == 0 and out_w:
             out["weighted"] = out_w
 
     # ---- the API surface, end to end: random_walk() -> DataFrame -> Node2VecGensim.fit() -> embedding() on cfg 2
-    if not args.no_api and world == 1 and rank == 0:
+    if full and not args.no_api and world == 1 and rank == 0:
         out["api"] = bench_api(args, torch, rw, dev)
 
     # ---- SGNS on the config's model ------------------------------------------------------------
     model = None
-    if not args.no_sgns:
+    if run_sgns:
         sg, model = bench_sgns(args, cfg, torch, dist, g, sg_walks, rank, world, barrier, use_dist, sg_blocks,
                                sg_vocab)
         if rank == 0:
             out["sgns"] = sg
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if full and rank == 0 and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(args, cfg, torch, g, start_all, W, L, p, q,
                                            sg_walks[: sg_walks.shape[0] // sg_blocks],
                                            model)
     if rank == 0:
         setup["hbm_peak_allocated_GB"] = torch.cuda.max_memory_allocated() / 1e9
         out["setup"] = setup
-        print(json.dumps(ordered_line(out)), flush=True)
+        print(json.dumps(ordered_line(out, summary=full)), flush=True)
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
@@ -714,13 +761,13 @@ def bench_api(args, torch, rw, dev):
     return res
 
 
-def ordered_line(out):
+def ordered_line(out, summary=True):
     """The ONE line, ordered for its readers: the contract's keys first; the bulky sub-objects
     (setup, sgns, fast_mode, the regimes) in the middle; at the END -- the part of a long line
     that a record keeping only a tail of stdout retains -- the API leg, the exact biased leg, the rooflines
     of the headline (`roofline`: vertex ids out, what random_walk() returns, reference fugue.py:153-155;
     `roofline_pipeline`: ranks out, what fit_streaming launches), the CPU baseline and a compact summary of
-    every leg."""
+    every leg (--full)."""
     head = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
             "scaling", "vs_baseline", "dtype", "data", "config"]
     tail = ["api", "biased", "cpu_baseline", "roofline_pipeline", "value_pipeline", "ms_per_step_pipeline",
@@ -729,6 +776,9 @@ def ordered_line(out):
     def frac(o):
         return None if not o or "roofline" not in o else round(o["roofline"]["frac"], 4)
 
+    keys = head + [k for k in out if k not in head and k not in tail] + [k for k in tail if k in out]
+    if not summary:
+        return {k: out[k] for k in keys if k in out}
     sg = out.get("sgns") or {}
     cpu = out.get("cpu_baseline") or {}
     out["summary"] = {

@@ -7,7 +7,7 @@ tail -1 gpurun_out/r14f_tests.log
 N2V_HOPS32=1 timeout -k 10 200 python scripts/fuzz_walk.py 60 23 > gpurun_out/r14f_fuzz.log 2>&1 || { tail -30 gpurun_out/r14f_fuzz.log; exit 1; }
 tail -1 gpurun_out/r14f_fuzz.log
 : > gpurun_out/r14f_time.log
-for h in 1 0; do N2V_HOPS32=$h timeout -k 10 400 python bench.py --config cfg5 --no-sgns --no-api --no-weighted --no-fast --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | python -c "
+for h in 1 0; do N2V_HOPS32=$h timeout -k 10 400 python bench.py --full --config cfg5 --no-sgns --no-api --no-weighted --no-fast --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | python -c "
 import sys,json
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('cfg5 hops32=$h', {k:round(v/1e9,2) for k,v in d['summary']['walk_steps_per_s'].items() if v})" >> gpurun_out/r14f_time.log; done
 for h in 0 1 0 1; do

@@ -9,7 +9,7 @@ for rep in 1 2; do
 for v in new kary0; do
   lib=$PWD/node2vec_amd/libn2v_hip.so
   [ $v = kary0 ] && lib=$PWD/build_variants/libn2v_wlanes_kary0.so
-  N2V_HIP_LIB=$lib timeout -k 10 400 python bench.py --no-sgns --no-api --no-fast --no-biased --no-ref-cap --no-cpu-baseline --steps 2 --warmup 1 2>/dev/null | python -c "
+  N2V_HIP_LIB=$lib timeout -k 10 400 python bench.py --full --no-sgns --no-api --no-fast --no-biased --no-ref-cap --no-cpu-baseline --steps 2 --warmup 1 2>/dev/null | python -c "
 import sys,json
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); w=d['weighted']; print('$v', w['value'], {k:v['value'] for k,v in w['small_batches'].items() if isinstance(v,dict) and 'value' in v})"
 done

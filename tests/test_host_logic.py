@@ -462,6 +462,46 @@ def test_bench_gpus_n_spawns_n_ranks(monkeypatch):
     assert "WORLD_SIZE=1" in str(e.value.code)
 
 
+def test_bench_plain_run_options_and_output_dump(tmp_path):
+    """bench.py times the headline alone unless --full is given; --dump-outputs writes the walks of the
+    headline's last step as float64, a fixed sample of rows when the launch is large (no GPU: CPU tensors)"""
+    import importlib.util
+
+    import numpy as np
+    import torch
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("n2v_bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse(["--steps", "7", "--warmup", "0"])
+    assert a.steps == 7 and a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path / "o")])
+    assert a.full is True and a.dump_outputs == str(tmp_path / "o")
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    gen = torch.Generator().manual_seed(5)
+    walks = torch.randint(-1, 2 ** 31 - 1, (5000, 81), generator=gen, dtype=torch.int32)
+    valid = (torch.arange(5000) % 3 != 0).to(torch.uint8)
+    bench.dump_outputs(str(tmp_path / "all"), walks, valid)
+    w = np.load(tmp_path / "all" / "walks.npy")
+    v = np.load(tmp_path / "all" / "valid.npy")
+    assert w.dtype == np.float64 and v.dtype == np.float64
+    assert np.array_equal(w, walks.numpy()) and np.array_equal(v, valid.numpy())
+    old = bench.DUMP_BYTES
+    try:
+        bench.DUMP_BYTES = 8 * 82 * 100  # 100 rows
+        for d in ("s1", "s2"):
+            bench.dump_outputs(str(tmp_path / d), walks, valid)
+    finally:
+        bench.DUMP_BYTES = old
+    s1, s2 = np.load(tmp_path / "s1" / "walks.npy"), np.load(tmp_path / "s2" / "walks.npy")
+    assert s1.shape == (100, 81) and np.array_equal(s1, s2)
+    rows = [int(np.flatnonzero((walks.numpy() == r).all(1))[0]) for r in s1]
+    assert rows == sorted(rows) and len(set(rows)) == 100
+    assert np.array_equal(np.load(tmp_path / "s1" / "valid.npy"), valid.numpy()[rows])
+
+
 def test_weighted_row_sums_and_the_grid_of_the_weights():
     """randomwalk.weighted_row_sums: what the margin kernels of weighted exact walks take the row sum of a step
     from -- per-row fp64 sums, then a power of two that divides every stored weight (fp32 storage only) and the

@@ -219,7 +219,7 @@ def test_bench_under_torchrun_rehearses_the_rccl_exchange():
 
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "cfg2", "--steps", "2",
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--config", "cfg2", "--steps", "2",
            "--warmup", "1", "--no-cpu-baseline", "--no-fast", "--no-regimes", "--no-biased",
            "--no-batched", "--no-hub"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -249,7 +249,7 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     import json
     import subprocess
 
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--config", "cfg2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--full", "--config", "cfg2",
            "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-fast", "--no-regimes", "--no-biased",
            "--no-batched", "--no-hub", "--no-api"]
     env = dict(os.environ)
