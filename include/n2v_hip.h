@@ -786,6 +786,36 @@ int n2v_rank_hops_build(const n2v_graph *g, const int32_t *rank_of, const int32_
 int n2v_mem_probe(void *buffer, int64_t buffer_bytes, int32_t mode, int32_t iters,
                   int32_t row_bytes, int64_t *accesses_host, uint32_t *sink, void *stream);
 
+/* Nearest neighbours by cosine over trained vectors: exact fp32 brute force over a row-major
+ * X[n, dim] (1 <= dim <= 1024, 0 <= n < 2^31), what gensim 3.8 KeyedVectors.init_sims /
+ * most_similar compute on the Word2Vec model the reference returns (embedding.py:120-127).
+ * score(q, r) = dot(q_hat, x_r) * inv_norm[r] with q_hat = q * (1 / sqrtf(sum q^2)) -- or, for a
+ * query given as row r' of X, x_r' * inv_norm[r'] -- in fp32 products and sums, every score in one
+ * fixed order (DESIGN.md "Nearest neighbours"): results do not depend on the batch of queries, and
+ * n2v_knn_topk's scores equal n2v_knn_scores' bit for bit.  A row (or query) of norm 0 scores 0
+ * where gensim gives NaN.  Exactly one of queries ([n_queries, dim] fp32) / query_rows
+ * ([n_queries] int64, each in [0, n)) is non-NULL.  Argument errors are N2V_EINVAL before any
+ * launch; n == 0 or n_queries == 0 is N2V_OK and launches nothing. */
+
+/* inv_norm[r] = 1 / sqrtf(sum_d X[r, d]^2), 0 for a zero row: init_sims' norms, without the
+ * normalised copy of X.  inv_norm: [n] fp32. */
+int n2v_knn_inv_norms(const float *X, int64_t n, int32_t dim, float *inv_norm, void *stream);
+/* Bytes of workspace n2v_knn_topk needs for these sizes (1 <= k <= 1024), or n2v_knn_scores
+ * (k == 0); -1 for sizes the calls refuse. */
+int64_t n2v_knn_workspace_bytes(int64_t n, int32_t dim, int64_t n_queries, int32_t k);
+/* The k best rows of every query (most_similar's argsort of the score vector, topn = k), fused:
+ * the n_queries x n score matrix is never written.  out_rows / out_scores: [n_queries, k] int64 /
+ * fp32, by score descending, then row ascending; for k > n the tail is row -1, score -inf.
+ * 1 <= k <= 1024; workspace: 16-byte aligned, workspace_bytes >= n2v_knn_workspace_bytes. */
+int n2v_knn_topk(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *queries,
+                 const int64_t *query_rows, int64_t n_queries, int32_t k, int64_t *out_rows,
+                 float *out_scores, void *workspace, int64_t workspace_bytes, void *stream);
+/* Every score (most_similar with topn=None): out_scores [n_queries, n] fp32, row-major.
+ * n_queries < 2^20; workspace as above with k == 0. */
+int n2v_knn_scores(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *queries,
+                   const int64_t *query_rows, int64_t n_queries, float *out_scores, void *workspace,
+                   int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,7 +27,8 @@ SYMBOLS = ("n2v_abi_version", "n2v_status_string", "n2v_device_count", "n2v_alia
            "n2v_partition_route", "n2v_partition_group", "n2v_walk_ws", "n2v_walk_workspace_bytes",
            "n2v_delta_reduce", "n2v_wedge_slots_build", "n2v_sgns_job_alpha", "n2v_rank_hops_build", "n2v_partition_forward",
            "n2v_sgns_hogwild_waves", "n2v_walk_weighted_step", "n2v_partition_forward_boxes", "n2v_walk_weighted_keys",
-           "n2v_wedge_slots_fold", "n2v_edge_row_sums_build")
+           "n2v_wedge_slots_fold", "n2v_edge_row_sums_build", "n2v_knn_inv_norms", "n2v_knn_workspace_bytes",
+           "n2v_knn_topk", "n2v_knn_scores")
 
 
 class WeightedHubs(C.Structure):
@@ -202,6 +203,16 @@ def load():
     L.n2v_mem_probe.restype = C.c_int
     L.n2v_mem_probe.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                 C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
+    L.n2v_knn_inv_norms.restype = C.c_int
+    L.n2v_knn_inv_norms.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+    L.n2v_knn_workspace_bytes.restype = C.c_int64
+    L.n2v_knn_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int32]
+    L.n2v_knn_topk.restype = C.c_int
+    L.n2v_knn_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                               C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.n2v_knn_scores.restype = C.c_int
+    L.n2v_knn_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     _lib = L
     return L
 

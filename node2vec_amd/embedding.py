@@ -147,6 +147,9 @@ class KeyedVectors:
             self.vocab = {t: i for i, t in enumerate(self.index2word)}
         self._vectors = vectors
         self.vector_size = int(vectors.shape[1]) if vectors.ndim == 2 else 0
+        # query caches (never saved): the matrix on the GPU, its inverse row norms (init_sims)
+        self._dev = vectors if isinstance(vectors, torch.Tensor) and vectors.is_cuda else None
+        self._inv_norm: Optional[torch.Tensor] = None
 
     @property
     def vectors(self) -> np.ndarray:
@@ -176,6 +179,115 @@ class KeyedVectors:
                 block = self.rows(lo, lo + chunk_rows).astype(np.float64).tolist()
                 toks = self.index2word[lo:lo + chunk_rows]
                 f.writelines(t + " " + " ".join(map(repr, v)) + "\n" for t, v in zip(toks, block))
+
+    # -- similarity queries (gensim 3.8 KeyedVectors; csrc/n2v_knn.hip) -----------------------
+    def _device_vectors(self) -> torch.Tensor:
+        """the matrix on the GPU: the trainer's tensor, or a copy of host vectors made on the first query"""
+        if self._dev is None:
+            from node2vec_amd import _lib
+
+            v = self._vectors
+            v = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))
+            self._dev = v.to(device=_lib.require_gpu(), dtype=torch.float32).contiguous()
+        return self._dev
+
+    def init_sims(self, replace: bool = False) -> None:
+        """Caches 1 / ||v|| of every row on the GPU (the normalised copy gensim builds is never made)."""
+        if replace:
+            raise NotImplementedError("init_sims(replace=True): the vectors are kept as trained")
+        if self._inv_norm is None:
+            from node2vec_amd import similarity
+
+            self._inv_norm = similarity.inv_norms(self._device_vectors())
+
+    def _row_of(self, token) -> int:
+        if isinstance(token, (int, np.integer)) and not isinstance(token, bool):
+            token = str(int(token))  # as get_vector
+        return self.vocab[token]  # KeyError for an unknown token
+
+    def _query(self, positive, negative):
+        """gensim 3.8 most_similar's mean: (unit query fp32 [dim], rows of the input tokens).  Tokens are
+        looked up (KeyError) and the input checked (ValueError) before the GPU is touched."""
+        def items(arg, weight):
+            if arg is None:
+                return []
+            if isinstance(arg, (str, int, np.integer, np.ndarray)):
+                arg = [arg]  # a bare token (or vector)
+            out = []
+            for it in arg:
+                if isinstance(it, tuple) and len(it) == 2 and not isinstance(it[0], tuple):
+                    out.append((it[0], float(it[1])))
+                else:
+                    out.append((it, weight))
+            return out
+
+        parsed = []
+        for item, weight in items(positive, 1.0) + items(negative, -1.0):
+            if isinstance(item, (np.ndarray, torch.Tensor)):
+                vec = np.asarray(item.cpu() if isinstance(item, torch.Tensor) else item, dtype=np.float32)
+                if vec.shape != (self.vector_size,):
+                    raise ValueError(f"a query vector must have {self.vector_size} values")
+                parsed.append((None, vec, weight))
+            else:
+                parsed.append((self._row_of(item), None, weight))
+        if not parsed:
+            raise ValueError("cannot compute similarity with no input")
+        mean = []
+        for row, vec, weight in parsed:
+            if row is not None:  # a token: its unit vector (gensim's vectors_norm row)
+                v = self.rows(row, row + 1)[0].astype(np.float32)
+                norm = np.float32(np.sqrt(np.dot(v, v)))
+                vec = v / norm if norm > 0 else v
+            mean.append(np.float32(weight) * vec)
+        mean = np.mean(np.asarray(mean, dtype=np.float32), axis=0, dtype=np.float32)
+        norm = np.float32(np.sqrt(np.dot(mean, mean)))
+        query = mean / norm if norm > 0 else mean
+        return query.astype(np.float32), sorted({row for row, _, _ in parsed if row is not None})
+
+    def most_similar(self, positive=None, negative=None, topn: Optional[int] = 10,
+                     restrict_vocab: Optional[int] = None):
+        """gensim 3.8 KeyedVectors.most_similar: [(token, cosine)] of the topn nearest rows to the unit mean of
+        weight * unit(token vector) (weight +1 for positive, -1 for negative, or given as (item, weight));
+        a vector given as such enters as it is, as in gensim.  The input tokens are not returned.
+        topn=None: the whole fp32 score array.  restrict_vocab: only the first rows are searched."""
+        if topn is not None and topn < 1:
+            return []
+        query, own = self._query(positive, negative)
+        from node2vec_amd import similarity
+
+        self.init_sims()
+        X = self._device_vectors()
+        q = torch.from_numpy(query).to(X.device)
+        if topn is None:
+            return similarity.scores(X, queries=q, restrict=restrict_vocab, inv_norm=self._inv_norm)[0].cpu().numpy()
+        rows, scores = similarity.knn(X, int(topn) + len(own), queries=q, restrict=restrict_vocab,
+                                      inv_norm=self._inv_norm)
+        rows, scores = rows[0].cpu().numpy(), scores[0].cpu().numpy()
+        own = set(own)
+        out = [(self.index2word[int(r)], float(s)) for r, s in zip(rows, scores) if r >= 0 and int(r) not in own]
+        return out[:int(topn)]
+
+    def similar_by_word(self, word, topn: Optional[int] = 10, restrict_vocab: Optional[int] = None):
+        return self.most_similar(positive=[word], topn=topn, restrict_vocab=restrict_vocab)
+
+    def similar_by_vector(self, vector, topn: Optional[int] = 10, restrict_vocab: Optional[int] = None):
+        return self.most_similar(positive=[np.asarray(vector, dtype=np.float32)], topn=topn,
+                                 restrict_vocab=restrict_vocab)
+
+    def similarity(self, w1, w2) -> float:
+        """cosine of two tokens (gensim: dot(unitvec(wv[w1]), unitvec(wv[w2])))"""
+        a, b = (self.rows(r, r + 1)[0].astype(np.float32) for r in (self._row_of(w1), self._row_of(w2)))
+        na, nb = np.float32(np.sqrt(np.dot(a, a))), np.float32(np.sqrt(np.dot(b, b)))
+        return float(np.dot(a / na if na > 0 else a, b / nb if nb > 0 else b))
+
+    def nearest(self, rows, topn: int = 10, exclude_self: bool = True, restrict_vocab: Optional[int] = None):
+        """The batched form: for every row number in `rows`, its topn nearest rows -- device tensors
+        (rows int64 [len(rows), topn], cosines fp32), best first, a query's own row left out."""
+        from node2vec_amd import similarity
+
+        self.init_sims()
+        return similarity.knn(self._device_vectors(), topn, rows=rows, restrict=restrict_vocab,
+                              inv_norm=self._inv_norm, exclude_self=exclude_self)
 
     @classmethod
     def load_word2vec_format(cls, fname: str) -> "KeyedVectors":
@@ -381,6 +493,22 @@ class Node2VecHIP(Node2VecBase):
         if isinstance(vertex_id, int):
             vertex_id = str(vertex_id)
         return list(self.model.wv[vertex_id])  # type: ignore
+
+    def most_similar(self, vertex_id: Union[str, int], topn: int = 10) -> pd.DataFrame:
+        """The topn vertices nearest to vertex_id by cosine of their vectors (model.wv.most_similar):
+        a DataFrame ["id" | "name", "similarity"], names mapped through name_id as in embedding()."""
+        if self.model is None:
+            raise ValueError("Model is not available. Please run fit()")
+        hits = self.model.wv.most_similar(str(vertex_id), topn=topn)
+        ids = np.array([int(t) for t, _ in hits], dtype=np.int64)
+        sims = np.array([s for _, s in hits], dtype=np.float64)
+        if self.name_id is None:
+            return pd.DataFrame({"id": ids, "similarity": sims})
+        names = self.name_id.drop_duplicates("id", keep="last").set_index("id")["name"]
+        missing = ~pd.Index(ids).isin(names.index)
+        if missing.any():
+            raise KeyError(int(ids[missing][0]))
+        return pd.DataFrame({"name": names.reindex(ids).to_numpy(), "similarity": sims})
 
     def save_model(self, file_path: str, file_name: str) -> None:
         """embedding.py:153-157: "<path>/<name>.model" """

@@ -1,0 +1,174 @@
+"""Nearest neighbours by cosine over trained vectors, on the GPU (csrc/n2v_knn.hip).
+
+What gensim 3.8 computes in KeyedVectors.init_sims / most_similar on the Word2Vec model the reference
+returns (embedding.py:120-127), without the normalised copy of the matrix and without the
+n_queries x n score matrix: the top k of every query are selected inside the scan.  Exact fp32, brute
+force; every score is computed in one fixed order, so results do not depend on how queries are batched
+(DESIGN.md "Nearest neighbours").  A row or query of norm 0 scores 0 (gensim: NaN).
+
+Device tensors in and out.  There is no CPU path: a missing GPU or library raises.
+"""
+from typing import Optional, Tuple
+
+import torch
+
+from node2vec_amd import _lib
+
+MAX_DIM = 1024
+MAX_FUSED_K = 1024  # n2v_knn_topk's limit; larger k go through the full scores and a stable sort
+WORKSPACE_LIMIT = 1 << 30  # bytes of workspace (or of full scores) per launch: query batches are split to fit
+
+
+def _matrix(X: torch.Tensor) -> torch.Tensor:
+    if not isinstance(X, torch.Tensor) or X.ndim != 2 or not X.is_cuda:
+        raise ValueError("X must be a 2-D tensor on a HIP device")
+    if X.dtype != torch.float32:
+        raise ValueError(f"X must be float32, not {X.dtype}")
+    if not 1 <= X.shape[1] <= MAX_DIM:
+        raise ValueError(f"vector dimension {X.shape[1]} outside [1, {MAX_DIM}]")
+    if X.shape[0] >= 1 << 31:
+        raise ValueError("at most 2^31 - 1 rows")
+    return X.contiguous()
+
+
+def inv_norms(X: torch.Tensor) -> torch.Tensor:
+    """1 / ||x_r|| for every row (0 for a zero row), fp32 [n]: the norms init_sims computes."""
+    X = _matrix(X)
+    out = torch.empty(X.shape[0], dtype=torch.float32, device=X.device)
+    with torch.cuda.device(X.device):
+        _lib.check(_lib.load().n2v_knn_inv_norms(X.data_ptr(), X.shape[0], X.shape[1], out.data_ptr(),
+                                                  _lib.current_stream_ptr()), "n2v_knn_inv_norms")
+    return out
+
+
+def _inputs(X, queries, rows, restrict, inv_norm):
+    """(X', inv_norm', queries, rows): X' the rows [0, restrict); a query row outside them becomes its vector"""
+    X = _matrix(X)
+    if (queries is None) == (rows is None):
+        raise ValueError("give exactly one of queries= / rows=")
+    n = X.shape[0]
+    if restrict is not None:
+        restrict = int(restrict)
+        if restrict < 0:
+            raise ValueError("restrict must be >= 0")
+    n_eff = n if restrict is None else min(restrict, n)
+    if inv_norm is None:
+        inv_norm = inv_norms(X[:n_eff])
+    elif inv_norm.ndim != 1 or inv_norm.shape[0] < n_eff:
+        raise ValueError("inv_norm must hold one value per row of X")
+    inv_norm = inv_norm[:n_eff].to(device=X.device, dtype=torch.float32).contiguous()
+    if rows is not None:
+        rows = torch.as_tensor(rows, device=X.device).to(torch.int64).reshape(-1).contiguous()
+        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= n):
+            raise IndexError("query row outside [0, n)")
+    else:
+        queries = torch.as_tensor(queries, device=X.device)
+        if queries.ndim == 1:
+            queries = queries[None]
+        if queries.ndim != 2 or queries.shape[1] != X.shape[1]:
+            raise ValueError(f"queries must be [n_queries, {X.shape[1]}]")
+        queries = queries.to(torch.float32).contiguous()
+    if restrict is not None and restrict < n:
+        if rows is not None:  # the same q_hat bit for bit: both forms normalise with the same sum
+            queries, rows = X[rows].contiguous(), None
+        X = X[:n_eff]
+    return X, inv_norm, queries, rows
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _scores(X, inv_norm, queries, rows) -> torch.Tensor:
+    L = _lib.load()
+    n, dim = X.shape
+    nq = (rows if rows is not None else queries).shape[0]
+    out = torch.empty((nq, n), dtype=torch.float32, device=X.device)
+    if n == 0 or nq == 0:
+        return out
+    ws = torch.empty(max(int(L.n2v_knn_workspace_bytes(n, dim, nq, 0)), 16), dtype=torch.uint8, device=X.device)
+    _lib.check(L.n2v_knn_scores(X.data_ptr(), inv_norm.data_ptr(), n, dim, _ptr(queries), _ptr(rows), nq,
+                                out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
+               "n2v_knn_scores")
+    return out
+
+
+def scores(X: torch.Tensor, queries=None, rows=None, restrict: Optional[int] = None,
+           inv_norm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Every score, fp32 [n_queries, n'] (n' = min(n, restrict)): most_similar's `dists` for topn=None.
+    Bit for bit the scores knn() selects from."""
+    X, inv_norm, queries, rows = _inputs(X, queries, rows, restrict, inv_norm)
+    with torch.cuda.device(X.device):
+        nq = (rows if rows is not None else queries).shape[0]
+        step = max(1, min(WORKSPACE_LIMIT // max(4 * X.shape[0], 1), (1 << 20) - 16))
+        parts = [_scores(X, inv_norm, None if queries is None else queries[i:i + step],
+                         None if rows is None else rows[i:i + step]) for i in range(0, nq, step)]
+    return torch.cat(parts) if len(parts) != 1 else parts[0]
+
+
+def _topk_fused(X, inv_norm, queries, rows, k):
+    L = _lib.load()
+    n, dim = X.shape
+    nq = (rows if rows is not None else queries).shape[0]
+    out_r = torch.full((nq, k), -1, dtype=torch.int64, device=X.device)
+    out_s = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=X.device)
+    if n == 0 or nq == 0:
+        return out_r, out_s
+    step = nq  # queries per launch: the workspace stays under WORKSPACE_LIMIT
+    while step > 1 and L.n2v_knn_workspace_bytes(n, dim, step, k) > WORKSPACE_LIMIT:
+        step = (step + 1) // 2
+    for i in range(0, nq, step):
+        j = min(nq, i + step)
+        ws = torch.empty(max(int(L.n2v_knn_workspace_bytes(n, dim, j - i, k)), 16), dtype=torch.uint8,
+                         device=X.device)
+        q = None if queries is None else queries[i:j]
+        r = None if rows is None else rows[i:j]
+        _lib.check(L.n2v_knn_topk(X.data_ptr(), inv_norm.data_ptr(), n, dim, _ptr(q), _ptr(r), j - i, k,
+                                  out_r[i:j].data_ptr(), out_s[i:j].data_ptr(), ws.data_ptr(), ws.numel(),
+                                  _lib.current_stream_ptr()), "n2v_knn_topk")
+    return out_r, out_s
+
+
+def _topk_sorted(X, inv_norm, queries, rows, k):
+    """k above the fused limit: full scores in batches, a stable descending sort (ties: row ascending)"""
+    n = X.shape[0]
+    nq = (rows if rows is not None else queries).shape[0]
+    out_r = torch.full((nq, k), -1, dtype=torch.int64, device=X.device)
+    out_s = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=X.device)
+    keep = min(k, n)
+    step = max(1, WORKSPACE_LIMIT // max(16 * n, 1))  # scores, sorted scores and int64 indices
+    for i in range(0, nq, step):
+        j = min(nq, i + step)
+        s = _scores(X, inv_norm, None if queries is None else queries[i:j], None if rows is None else rows[i:j])
+        s, idx = torch.sort(s, dim=1, descending=True, stable=True)
+        out_r[i:j, :keep], out_s[i:j, :keep] = idx[:, :keep], s[:, :keep]
+    return out_r, out_s
+
+
+def knn(X: torch.Tensor, k: int, queries=None, rows=None, restrict: Optional[int] = None,
+        inv_norm: Optional[torch.Tensor] = None, exclude_self: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k rows of X nearest to every query by cosine: (rows int64 [nq, k], scores fp32 [nq, k]), by score
+    descending, then row ascending; where fewer than k rows exist the tail is row -1, score -inf.
+
+    queries: [nq, dim] (or [dim]) vectors, or rows: [nq] row numbers of X -- exactly one.  restrict: only rows
+    [0, restrict) are candidates (gensim's restrict_vocab).  inv_norm: inv_norms(X), cached by the caller.
+    exclude_self (rows= only): a query's own row is not returned (k + 1 are asked for)."""
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    if exclude_self and rows is None:
+        raise ValueError("exclude_self needs rows=")
+    X, inv_norm, queries, qrows = _inputs(X, queries, rows, restrict, inv_norm)
+    self_rows = None
+    if exclude_self:
+        self_rows = torch.as_tensor(rows, device=X.device).to(torch.int64).reshape(-1)
+    want = k + 1 if exclude_self else k
+    with torch.cuda.device(X.device):
+        pick = _topk_fused if want <= MAX_FUSED_K else _topk_sorted
+        out_r, out_s = pick(X, inv_norm, queries, qrows, want)
+    if not exclude_self:
+        return out_r, out_s
+    drop = out_r == self_rows[:, None]
+    drop[:, -1] |= ~drop.any(dim=1)  # not among the k + 1: the last one goes
+    keep = ~drop
+    return out_r[keep].view(-1, k), out_s[keep].view(-1, k)
