@@ -233,7 +233,9 @@ __global__ __launch_bounds__(kWaves * 64) void topk_chunk_kernel(
         for (int i = 0; i < 4; ++i) {
           const int64_t r = row0 + 4 * (lane >> 4) + i;
           const float s = acc[g][i] * inv[i];
-          if (r < hi && s >= t) {  // ties with the threshold may still win on the row
+          // a tie with the threshold cannot win (its row is above every kept row: rows arrive in ascending
+          // order within a chunk), so s >= t keeps nothing s > t would not need; NaN fails both
+          if (r < hi && s >= t) {
             const int pos = atomicAdd(&cnt[q], 1);
             buf_s[q][pos] = s;
             buf_r[q][pos] = (int32_t)r;

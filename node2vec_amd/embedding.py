@@ -249,7 +249,9 @@ class KeyedVectors:
         """gensim 3.8 KeyedVectors.most_similar: [(token, cosine)] of the topn nearest rows to the unit mean of
         weight * unit(token vector) (weight +1 for positive, -1 for negative, or given as (item, weight));
         a vector given as such enters as it is, as in gensim.  The input tokens are not returned.
-        topn=None: the whole fp32 score array.  restrict_vocab: only the first rows are searched."""
+        topn=None: the whole fp32 score array.  restrict_vocab: only the first rows are searched.
+        A row holding inf or NaN (or a query that does) scores NaN: it is never returned, for every topn, so
+        fewer than topn pairs may come back; topn=None returns the NaN scores."""
         if topn is not None and topn < 1:
             return []
         query, own = self._query(positive, negative)

@@ -4,7 +4,8 @@ What gensim 3.8 computes in KeyedVectors.init_sims / most_similar on the Word2Ve
 returns (embedding.py:120-127), without the normalised copy of the matrix and without the
 n_queries x n score matrix: the top k of every query are selected inside the scan.  Exact fp32, brute
 force; every score is computed in one fixed order, so results do not depend on how queries are batched
-(DESIGN.md "Nearest neighbours").  A row or query of norm 0 scores 0 (gensim: NaN).
+(DESIGN.md "Nearest neighbours").  A row or query of norm 0 scores 0 (gensim: NaN).  A row or query holding
+inf or NaN scores NaN; knn() never selects a NaN score.
 
 Device tensors in and out.  There is no CPU path: a missing GPU or library raises.
 """
@@ -130,18 +131,24 @@ def _topk_fused(X, inv_norm, queries, rows, k):
 
 
 def _topk_sorted(X, inv_norm, queries, rows, k):
-    """k above the fused limit: full scores in batches, a stable descending sort (ties: row ascending)"""
+    """k above the fused limit: full scores in batches, a stable descending sort (ties: row ascending).
+    A NaN score is absent, as in the fused kernel: it sorts last and leaves (-1, -inf)."""
     n = X.shape[0]
     nq = (rows if rows is not None else queries).shape[0]
     out_r = torch.full((nq, k), -1, dtype=torch.int64, device=X.device)
     out_s = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=X.device)
     keep = min(k, n)
-    step = max(1, WORKSPACE_LIMIT // max(16 * n, 1))  # scores, sorted scores and int64 indices
+    # scores, sorted scores and int64 indices; n2v_knn_scores takes at most 65 535 x 16 queries
+    step = max(1, min(WORKSPACE_LIMIT // max(16 * n, 1), (1 << 20) - 16))
     for i in range(0, nq, step):
         j = min(nq, i + step)
         s = _scores(X, inv_norm, None if queries is None else queries[i:j], None if rows is None else rows[i:j])
+        # no real score is -inf (a row's norm is finite or its inv_norm 0), so -inf marks the absent
+        s = s.masked_fill_(torch.isnan(s), float("-inf"))
         s, idx = torch.sort(s, dim=1, descending=True, stable=True)
-        out_r[i:j, :keep], out_s[i:j, :keep] = idx[:, :keep], s[:, :keep]
+        s, idx = s[:, :keep], idx[:, :keep]
+        out_r[i:j, :keep] = idx.masked_fill_(s == float("-inf"), -1)
+        out_s[i:j, :keep] = s
     return out_r, out_s
 
 
@@ -152,7 +159,11 @@ def knn(X: torch.Tensor, k: int, queries=None, rows=None, restrict: Optional[int
 
     queries: [nq, dim] (or [dim]) vectors, or rows: [nq] row numbers of X -- exactly one.  restrict: only rows
     [0, restrict) are candidates (gensim's restrict_vocab).  inv_norm: inv_norms(X), cached by the caller.
-    exclude_self (rows= only): a query's own row is not returned (k + 1 are asked for)."""
+    exclude_self (rows= only): a query's own row is not returned (k + 1 are asked for).
+
+    Non-finite input: a row or query holding inf or NaN scores NaN, and a NaN score is never selected, for
+    every k -- such rows are left out like absent ones, so the tail may start early (row -1, score -inf).
+    scores() returns the NaN itself."""
     k = int(k)
     if k < 1:
         raise ValueError("k must be >= 1")

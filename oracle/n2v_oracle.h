@@ -12,6 +12,8 @@
  * against the known-answer values of the reference's tests/test_randomwalk.py.
  * The SGNS half lives in n2v_oracle_sgns.c and is "parity unpinned" (its
  * arithmetic is third-party gensim, absent from /root/reference).
+ * n2v_oracle_knn.c restates the project's own nearest-neighbour kernels (no
+ * reference counterpart): the claim is GPU == restatement, bit for bit.
  *
  * All citations are file:line relative to /root/reference/.
  */
@@ -121,6 +123,18 @@ int64_t n2v_oracle_sgns_train_batched(const int32_t *walks, int64_t n_walks, int
                               const uint32_t *sample_int, const float *exp_table,
                               int64_t n_vocab, int64_t sentence_base, uint64_t seed,
                               int32_t dim, int32_t window, int32_t negative, float alpha);
+
+/* n2v_oracle_knn.c: the nearest-neighbour kernels of node2vec_amd/csrc/n2v_knn.hip restated in their
+ * fp32 order (see its header).  Queries as vectors [nq, dim] or as row numbers of X -- exactly one. */
+int n2v_oracle_knn_inv_norms(const float *X, int64_t n, int32_t dim, float *inv_norm);
+/* out [nq, n]; order 0: the kernels' summation order, 1: sequential d (to show the first is specific) */
+int n2v_oracle_knn_scores(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *queries,
+                          const int64_t *query_rows, int64_t nq, int32_t order, float *out);
+/* out [nq, k]: score descending, then row ascending, no NaN score, tail (-1, -inf); exclude_rows
+ * (NULL or [nq]): a row left out of query q's candidates (-1: none) */
+int n2v_oracle_knn_topk(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *queries,
+                        const int64_t *query_rows, int64_t nq, int32_t k, const int64_t *exclude_rows,
+                        int64_t *out_rows, float *out_scores);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,9 @@ def lib():
         L.n2v_oracle_edge_classes.restype = C.c_int
         L.n2v_oracle_sgns_train.restype = C.c_int64
         L.n2v_oracle_sgns_train_batched.restype = C.c_int64
+        L.n2v_oracle_knn_inv_norms.restype = C.c_int
+        L.n2v_oracle_knn_scores.restype = C.c_int
+        L.n2v_oracle_knn_topk.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -209,3 +212,74 @@ def trim_mark(rowptr, max_out_degree, seed):
     _raise(lib().n2v_oracle_trim_mark(_p(rowptr), C.c_int64(len(rowptr) - 1),
                                       C.c_int64(max_out_degree), C.c_uint64(seed), _p(keep)))
     return keep.astype(bool)
+
+
+def _knn_args(X, inv_norm, queries, rows):
+    X = np.ascontiguousarray(X, np.float32)
+    assert X.ndim == 2
+    inv = knn_inv_norms(X) if inv_norm is None else np.ascontiguousarray(inv_norm, np.float32)
+    if (queries is None) == (rows is None):
+        raise ValueError("give exactly one of queries= / rows=")
+    if rows is not None:
+        rows = np.ascontiguousarray(rows, np.int64).reshape(-1)
+        nq = len(rows)
+    else:
+        queries = np.ascontiguousarray(queries, np.float32).reshape(-1, X.shape[1])
+        nq = queries.shape[0]
+    return X, inv, queries, rows, nq
+
+
+def knn_inv_norms(X):
+    """oracle/n2v_oracle_knn.c: 1 / sqrtf(sum x^2) per row in the kernel's order (0 for a zero row)"""
+    X = np.ascontiguousarray(X, np.float32)
+    out = np.zeros(max(X.shape[0], 1), np.float32)
+    _raise(lib().n2v_oracle_knn_inv_norms(_p(X), C.c_int64(X.shape[0]), C.c_int32(X.shape[1]), _p(out)))
+    return out[:X.shape[0]]
+
+
+def knn_scores(X, queries=None, rows=None, inv_norm=None, order=0):
+    """every score [nq, n] (order 0: the kernels' summation order; 1: sequential d)"""
+    X, inv, queries, rows, nq = _knn_args(X, inv_norm, queries, rows)
+    out = np.zeros((max(nq, 1), max(X.shape[0], 1)), np.float32)[:nq, :X.shape[0]].copy()
+    _raise(lib().n2v_oracle_knn_scores(_p(X), _p(inv), C.c_int64(X.shape[0]), C.c_int32(X.shape[1]),
+                                       None if queries is None else _p(queries), None if rows is None else _p(rows),
+                                       C.c_int64(nq), C.c_int32(order), _p(out)))
+    return out
+
+
+def knn_topk(X, k, queries=None, rows=None, inv_norm=None, exclude=None):
+    """(rows int64 [nq, k], scores fp32 [nq, k]): score descending, then row ascending; NaN never
+    selected; tail (-1, -inf).  exclude: [nq] a row left out of each query's candidates (-1: none)"""
+    X, inv, queries, rows, nq = _knn_args(X, inv_norm, queries, rows)
+    out_r = np.zeros((nq, k), np.int64)
+    out_s = np.zeros((nq, k), np.float32)
+    ex = None if exclude is None else np.ascontiguousarray(exclude, np.int64).reshape(-1)
+    _raise(lib().n2v_oracle_knn_topk(_p(X), _p(inv), C.c_int64(X.shape[0]), C.c_int32(X.shape[1]),
+                                     None if queries is None else _p(queries), None if rows is None else _p(rows),
+                                     C.c_int64(nq), C.c_int32(k), None if ex is None else _p(ex),
+                                     _p(out_r), _p(out_s)))
+    return out_r, out_s
+
+
+def knn_plan(n, dim, nq, k):
+    """plan_topk of csrc/n2v_knn.hip restated: (variant, queries per block, n_chunks, chunk_rows, workspace
+    bytes).  variant 0: G 4 / 64 queries / CAP 256, 1: G 2 / 32 / 512, 2: G 1 / 16 / 1024, 3: G 1 / 8 / 2048"""
+    def up(a, b):
+        return (a + b - 1) // b * b
+    if k <= 128 and nq > 32:
+        variant, qt = 0, 64
+    elif k <= 384 and nq > 16:
+        variant, qt = 1, 32
+    elif k <= 896:
+        variant, qt = 2, 16
+    else:
+        variant, qt = 3, 8
+    tiles = (nq + qt - 1) // qt
+    step_rows = 128  # 8 waves x 16 rows
+    chunks = min((512 + tiles - 1) // tiles, (n + 16 * step_rows - 1) // (16 * step_rows))
+    chunks = max(chunks, 1)
+    chunk_rows = up((n + chunks - 1) // chunks, step_rows)
+    n_chunks = max((n + chunk_rows - 1) // chunk_rows, 1)
+    qhat = up((up(nq, 64) + 16) * up(dim, 16) * 4, 256)
+    part = up(nq * n_chunks * k * 4, 256)
+    return variant, qt, n_chunks, chunk_rows, qhat + 4 * part
