@@ -816,6 +816,51 @@ int n2v_knn_scores(const float *X, const float *inv_norm, int64_t n, int32_t dim
                    const int64_t *query_rows, int64_t n_queries, float *out_scores, void *workspace,
                    int64_t workspace_bytes, void *stream);
 
+/* Skip-gram with HIERARCHICAL SOFTMAX (what Spark ML's Word2Vec trains behind the reference's
+ * Node2VecSpark, embedding.py:182-285): word2vec.c's Huffman tree and skip-gram HS update,
+ * DESIGN.md "Hierarchical softmax".
+ *
+ * n2v_hs_tree_build (host memory, no GPU): the Huffman tree of counts[n_vocab] (descending, as
+ * the vocabulary is ordered; >= 0), built exactly as word2vec.c CreateBinaryTree.  Word w's path
+ * is points[path_off[w] .. path_off[w + 1]) (syn1 rows, root n_vocab - 2 first) and its code bit d
+ * is (codes[w] >> d) & 1.  path_off_out: [n_vocab + 1] int64, codes_out: [n_vocab] uint64,
+ * points_out: [path_off[n_vocab]] int32 or NULL (then only path_off / codes are written: the caller
+ * sizes points from path_off[n_vocab] and calls again).  N2V_EINVAL for counts that are not
+ * descending, a code longer than 64 bits, or points_capacity < path_off[n_vocab].  n_vocab == 1:
+ * code length 0. */
+int n2v_hs_tree_build(const int64_t *counts, int64_t n_vocab, int64_t *path_off_out, uint64_t *codes_out,
+                      int32_t *points_out, int64_t points_capacity);
+
+typedef struct n2v_hs_params {
+  int64_t n_vocab;
+  int64_t sentence_base; /* global index of walks[0] (RNG key) */
+  uint64_t seed;
+  int32_t dim;           /* 1 .. 1024 */
+  int32_t window;        /* 1 .. 32 */
+  float alpha;           /* rate of every row when row_alpha is NULL */
+  int32_t deterministic; /* 1: one wave, rows in order: bit-identical to the CPU restatement */
+  const float *row_alpha; /* [n_walks] or NULL: the rate of every row of the launch */
+  int32_t max_waves;     /* 0: one wave per 32 vocabulary rows, up to the whole chip */
+  int32_t hot_nodes;     /* must be 0 (N2V_EINVAL otherwise): atomic adds on the nodes nearest the root
+                            were measured slower and worse than plain stores */
+  int32_t path_cache;    /* 1: the top path rows of a centre position are held in LDS across its
+                            contexts (same values); 0: every pair reads and writes them in HBM */
+  int32_t reserved;
+} n2v_hs_params;
+
+/* One pass of skip-gram HS over a block of rows.  walks: [n_walks, walk_len] int32 vocabulary
+ * indices (< 0 or >= n_vocab: dropped before windowing; walk_len <= N2V_SGNS_MAX_SENTENCE); syn0
+ * [n_vocab, dim], syn1 [n_vocab - 1, dim] fp32 in place; path_off / points / codes from
+ * n2v_hs_tree_build, on the device; exp_table [1000] fp32; pairs_out: TWO device uint64 or NULL,
+ * as n2v_sgns_train.  Argument errors are N2V_EINVAL before anything is launched. */
+int n2v_hs_train(const int32_t *walks, int64_t n_walks, int32_t walk_len, float *syn0, float *syn1,
+                 const int64_t *path_off, const int32_t *points, const uint64_t *codes, const float *exp_table,
+                 const n2v_hs_params *params_host, unsigned long long *pairs_out, void *stream);
+
+/* The waves n2v_hs_train keeps in flight for such a launch on this device (nothing is launched), or
+ * a negative status for parameters it would refuse. */
+int64_t n2v_hs_hogwild_waves(const n2v_hs_params *P, int64_t n_walks, int32_t walk_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,7 @@ SYMBOLS = ("n2v_abi_version", "n2v_status_string", "n2v_device_count", "n2v_alia
            "n2v_delta_reduce", "n2v_wedge_slots_build", "n2v_sgns_job_alpha", "n2v_rank_hops_build", "n2v_partition_forward",
            "n2v_sgns_hogwild_waves", "n2v_walk_weighted_step", "n2v_partition_forward_boxes", "n2v_walk_weighted_keys",
            "n2v_wedge_slots_fold", "n2v_edge_row_sums_build", "n2v_knn_inv_norms", "n2v_knn_workspace_bytes",
-           "n2v_knn_topk", "n2v_knn_scores")
+           "n2v_knn_topk", "n2v_knn_scores", "n2v_hs_tree_build", "n2v_hs_train", "n2v_hs_hogwild_waves")
 
 
 class WeightedHubs(C.Structure):
@@ -62,6 +62,14 @@ class SgnsParams(C.Structure):
                 ("alpha", C.c_float), ("deterministic", C.c_int32), ("cum_index_bits", C.c_int32),
                 ("cum_index", C.c_void_p), ("max_waves", C.c_int32), ("batched", C.c_int32),
                 ("window_cache", C.c_int32), ("hub_rows", C.c_int32), ("row_alpha", C.c_void_p)]
+
+
+class HsParams(C.Structure):
+    """struct n2v_hs_params"""
+    _fields_ = [("n_vocab", C.c_int64), ("sentence_base", C.c_int64), ("seed", C.c_uint64),
+                ("dim", C.c_int32), ("window", C.c_int32), ("alpha", C.c_float), ("deterministic", C.c_int32),
+                ("row_alpha", C.c_void_p), ("max_waves", C.c_int32), ("hot_nodes", C.c_int32),
+                ("path_cache", C.c_int32), ("reserved", C.c_int32)]
 
 
 _lib = None
@@ -213,6 +221,13 @@ def load():
     L.n2v_knn_scores.restype = C.c_int
     L.n2v_knn_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                  C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.n2v_hs_tree_build.restype = C.c_int
+    L.n2v_hs_tree_build.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    L.n2v_hs_train.restype = C.c_int
+    L.n2v_hs_train.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.POINTER(HsParams), C.c_void_p, C.c_void_p]
+    L.n2v_hs_hogwild_waves.restype = C.c_int64
+    L.n2v_hs_hogwild_waves.argtypes = [C.POINTER(HsParams), C.c_int64, C.c_int32]
     _lib = L
     return L
 

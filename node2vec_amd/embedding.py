@@ -24,7 +24,7 @@ import pandas as pd
 import torch
 
 from node2vec_amd import corpus, sgns
-from node2vec_amd.constants import GENSIM_PARAMS, HIP_SGNS_PARAMS
+from node2vec_amd.constants import GENSIM_PARAMS, HIP_SGNS_PARAMS, WORD2VEC_PARAMS
 
 
 class Node2VecBase(object):
@@ -529,6 +529,163 @@ class Node2VecHIP(Node2VecBase):
     def load_vectors(file_path: str, file_name: str) -> KeyedVectors:
         """embedding.py:172-178"""
         return KeyedVectors.load_word2vec_format(os.path.join(file_path, file_name))
+
+
+class HsW2VModel:
+    """The fitted model of Node2VecSpark (stands where Spark's Word2VecModel stands): .wv over syn0
+    (so most_similar works), the inner-node matrix syn1, the parameters and what the trainer did."""
+
+    FILE = "model.pt"
+
+    def __init__(self, wv: KeyedVectors, syn1, params: Dict[str, Any], pairs: int, stats: Dict[str, Any]):
+        self.wv, self._syn1, self.params, self.pairs_trained = wv, syn1, dict(params), pairs
+        self.stats = dict(stats)
+
+    @property
+    def syn1(self) -> np.ndarray:
+        if isinstance(self._syn1, torch.Tensor):
+            self._syn1 = self._syn1.cpu().numpy()
+        return self._syn1
+
+    def getVectors(self) -> pd.DataFrame:
+        """Spark's Word2VecModel.getVectors: ["word", "vector"], one row per vocabulary word (words are
+        the int64 vertex ids, where Spark has the strings of its array<string> cast)"""
+        from node2vec_amd import corpus
+
+        wv = self.wv
+        ids = wv.ids if wv.ids is not None else np.array([int(t) for t in wv.index2word], dtype=np.int64)
+        return pd.DataFrame({"word": ids, "vector": corpus.list_column(wv.rows(0, len(wv)), "list")})
+
+    def save(self, path: str) -> None:
+        """a directory (Spark writes one), overwritten"""
+        os.makedirs(path, exist_ok=True)
+        tokens = self.wv.ids if self.wv.ids is not None else self.wv.index2word
+        torch.save({"tokens": tokens, "vectors": self.wv.vectors, "syn1": self.syn1, "params": self.params,
+                    "pairs": self.pairs_trained, "stats": self.stats}, os.path.join(path, self.FILE))
+
+    @classmethod
+    def load(cls, path: str) -> "HsW2VModel":
+        d = torch.load(os.path.join(path, cls.FILE), weights_only=False)
+        return cls(KeyedVectors(d["tokens"], d["vectors"]), d["syn1"], d["params"], d["pairs"], d["stats"])
+
+
+# the keyword arguments Spark's Word2Vec takes besides inputCol / outputCol (the reference sets those),
+# and the options of the HIP trainer
+_SPARK_KEYS = frozenset(WORD2VEC_PARAMS)
+HIP_HS_PARAMS: Dict[str, Any] = {
+    "deterministic": False,  # True: one wave, sentences in order -- reproducible bit for bit (for tests)
+}
+
+
+class Node2VecSpark(Node2VecBase):
+    """Drop-in for the reference's Node2VecSpark (embedding.py:182-285) on one MI355X: skip-gram with
+    hierarchical softmax, what Spark ML's Word2Vec trains (node2vec_amd/hs.py, csrc/n2v_hs.hip).
+
+    Deviations: words are int64 vertex ids where Spark casts the walks to array<string>; numPartitions
+    is validated but not replayed (Spark trains that many replicas per iteration and averages them:
+    this trainer keeps one model); Spark's vocabSize * vectorSize < 2^31 cap is not replayed; sentences
+    longer than 256 tokens are cut at 256 (the kernel's row buffer)."""
+
+    def __init__(
+        self,
+        df_walks,
+        w2v_params: Dict[str, Any],
+        name_id: Optional[pd.DataFrame] = None,
+        window_size: Optional[int] = None,
+        vector_size: Optional[int] = None,
+        random_seed: Optional[int] = None,
+    ) -> None:
+        super().__init__()
+        self.walks = df_walks
+        self.name_id = name_id
+        self.model: Optional[HsW2VModel] = None
+
+        for param in WORD2VEC_PARAMS:  # embedding.py:234-236: fills the caller's dict
+            if param not in w2v_params:
+                w2v_params[param] = WORD2VEC_PARAMS[param]
+        w2v_params["seed"] = random_seed if random_seed else int(time.time())  # :237
+        if window_size is not None:
+            if window_size < 5 or window_size > 30:  # :238-241
+                raise ValueError(f"Inappropriate context window size {window_size}!")
+            w2v_params["windowSize"] = window_size
+        if vector_size is not None:
+            if vector_size < 32 or vector_size > 1024:  # :242-245
+                raise ValueError(f"Inappropriate vector dimension {vector_size}!")
+            w2v_params["vectorSize"] = vector_size
+        unknown = sorted(k for k in w2v_params if k not in _SPARK_KEYS and k not in HIP_HS_PARAMS)
+        if unknown:  # Spark's keyword-only constructor
+            raise TypeError(f"Word2Vec got an unexpected keyword argument {unknown[0]!r}")
+        for k in ("vectorSize", "windowSize", "stepSize", "numPartitions", "maxSentenceLength"):
+            if not w2v_params[k] > 0:
+                raise ValueError(f"{k} must be positive, got {w2v_params[k]!r}")
+        for k in ("maxIter", "minCount"):
+            if w2v_params[k] < 0:
+                raise ValueError(f"{k} must be >= 0, got {w2v_params[k]!r}")
+        if w2v_params["vectorSize"] > 1024 or w2v_params["windowSize"] > 32:
+            raise ValueError("the HIP trainer supports vectorSize <= 1024 and windowSize <= 32")
+        logging.info(f"__init__(): w2v params: {w2v_params}")
+        self.w2v_params = w2v_params
+
+    def fit(self, device=None) -> HsW2VModel:
+        """Trains and returns the model (embedding.py:247-256).  One GPU: under a process group of more
+        than one rank it raises NotImplementedError."""
+        import torch.distributed as dist
+
+        from node2vec_amd import _lib, hs
+
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("Node2VecSpark trains on one GPU: there is no multi-GPU hierarchical softmax")
+        dev = device or _lib.require_gpu()
+        p = dict(HIP_HS_PARAMS)
+        p.update(self.w2v_params)
+        walks = Node2VecHIP._walk_tensor(self, dev)
+        vocab = sgns.build_vocab(walks, int(p["minCount"]))
+        if len(vocab) == 0:
+            raise RuntimeError("you must first build vocabulary before training the model")
+        idx = torch.where(walks >= 0, vocab.index_of[walks.clamp(min=0).long()], torch.full_like(walks, -1))
+        rows = hs.sentences(idx, int(p["maxSentenceLength"]))
+        m = hs.HsModel(vocab, int(p["vectorSize"]), int(p["windowSize"]), int(p["seed"]), device=dev)
+        m.train(rows, int(p["maxIter"]), float(p["stepSize"]), deterministic=bool(p.get("deterministic")))
+        torch.cuda.synchronize(dev)
+        stats = {"hogwild_waves": m.hogwild_waves_used,
+                 "hot_nodes": hs.HOT_NODES,
+                 "mean_code_length": m.mean_code_length, "sentences": int(rows.shape[0])}
+        self.model = HsW2VModel(KeyedVectors(vocab.ids, m.syn0), m.syn1, p, int(m.pairs.item()), stats)
+        logging.info("model fitting done!")
+        return self.model
+
+    def embedding(self) -> pd.DataFrame:
+        """embedding.py:258-267: ["id", "vector"], or ["name", "vector"] through an inner join with
+        name_id (ids that name_id does not list are dropped, as Spark's join drops them)"""
+        if self.model is None:
+            raise ValueError("Model is not available. Please run fit()")
+        df = self.model.getVectors().rename(columns={"word": "id"})
+        if self.name_id is not None:
+            df = df.merge(self.name_id, on="id", how="inner")[["name", "vector"]]
+        return df
+
+    def get_vector(self, vertex_id: Union[str, int]) -> pd.DataFrame:
+        """embedding.py:269-274: the ["word", "vector"] rows of word == vertex_id (0 or 1 row)"""
+        if self.model is None:
+            raise ValueError("Model is not available. Please run fit()")
+        wv = self.model.wv
+        row = wv.vocab.get(str(vertex_id))
+        if row is None:
+            return pd.DataFrame({"word": np.array([], np.int64), "vector": []})
+        word = int(wv.ids[row]) if wv.ids is not None else int(wv.index2word[row])
+        return pd.DataFrame({"word": np.array([word], np.int64), "vector": [wv.rows(row, row + 1)[0].tolist()]})
+
+    def save_model(self, cloud_path: str, model_name: str) -> None:
+        """embedding.py:276-285: "<path>/<name>.sparkml", a directory"""
+        if not model_name.endswith(".sparkml"):
+            model_name += ".sparkml"
+        self.model.save(os.path.join(cloud_path, model_name))  # type: ignore
+
+    def load_model(self, cloud_path: str, model_name: str) -> HsW2VModel:
+        if not model_name.endswith(".sparkml"):
+            model_name += ".sparkml"
+        self.model = HsW2VModel.load(os.path.join(cloud_path, model_name))
+        return self.model
 
 
 # import-compatible names
