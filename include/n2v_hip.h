@@ -123,9 +123,14 @@ typedef struct n2v_graph {
   /* The degree-ranked form of a unit-weight graph (p == q == 1 walks; n2v_rank_hops_build), or all
    * NULL / 0.  Vertices are numbered again by descending degree (`rank`), rows are laid out in rank
    * order, so the row of a rank follows from the DEGREE CLASS the rank falls in and an entry of the
-   * table is the 4-byte rank of the neighbour alone: a step is one 4-byte gather. */
+   * table is the 4-byte rank of the neighbour alone: a step is one 4-byte gather.
+   * The pair table (n2v_rank_pairs_build) is the same layout with 8-byte entries
+   * (uint64_t)rank << 32 | vertex id: a walk that writes VERTEX IDS in one 8-byte gather per step, on any
+   * graph the ranked form accepts.  A caller passes it through the same fields: rank_hops points at the
+   * uint64 entries and rank_emit is 2 (rank_vertex is not read). */
   const uint32_t *rank_hops;        /* [n_edges]: rank of every neighbour; rows in rank order, the entries
-                                       of a row in the CSR's order (so pick = int(r1 * n) is unchanged) */
+                                       of a row in the CSR's order (so pick = int(r1 * n) is unchanged).
+                                       rank_emit == 2: const uint64_t [n_edges], the pair table */
   const int32_t *rank_of;           /* [n_vertices]: vertex id -> rank */
   const int32_t *rank_vertex;       /* [n_vertices]: rank -> vertex id */
   const uint64_t *rank_head;        /* [rank_head_n]: row offset | degree << 40 of ranks below rank_head_n
@@ -142,7 +147,9 @@ typedef struct n2v_graph {
   int32_t rank_emit;                /* what the ranked kernel writes to walks_out: 0 = vertex ids (one more
                                        gather per token through rank_vertex), 1 = ranks (the caller
                                        composes rank_vertex into its own per-token lookup, as
-                                       n2v_corpus_index's index_of) */
+                                       n2v_corpus_index's index_of), 2 = vertex ids, and rank_hops points
+                                       at the 8-byte pair table of n2v_rank_pairs_build (no second
+                                       gather).  Any other value: N2V_EINVAL */
   int32_t reserved3;                /* 0 */
   /* Row sums of the tables of the steps into LONG rows, for ONE (p, q) whose 1/p or 1/q is not dyadic
    * (n2v_edge_row_sums_build; ABI 15), or NULL / 0.  The walk kernels ignore the table unless row_sums_p / _q are
@@ -763,6 +770,17 @@ int n2v_gather_wedges(const uint32_t *edge_classes, const uint64_t *wedge_off, c
  * out: [g->n_edges] uint32. */
 int n2v_rank_hops_build(const n2v_graph *g, const int32_t *rank_of, const int32_t *rank_vertex,
                         const int64_t *rank_rowptr, uint32_t *out, void *stream);
+
+/* The pair table: the rows of n2v_rank_hops_build (same arguments, same order of rows and of the entries
+ * inside a row) with 8-byte entries that hold the neighbour's vertex id beside its rank:
+ *   out[rank_rowptr[r] + k] = (uint64_t)rank_of[c] << 32 | (uint32_t)c,  c = col[rowptr[rank_vertex[r]] + k].
+ * A p == q == 1 walk over it (n2v_graph.rank_hops = out, rank_emit = 2, the head and class tables as for
+ * the ranked form) writes the low word to the path and finds the next row from the high word: vertex
+ * ids out in one 8-byte gather per step, where the 4-byte form needs a second gather through
+ * rank_vertex and the 8-byte hop table (n2v_hops8_build) needs field widths the graph may not have.
+ * out: [g->n_edges] uint64. */
+int n2v_rank_pairs_build(const n2v_graph *g, const int32_t *rank_of, const int32_t *rank_vertex,
+                         const int64_t *rank_rowptr, uint64_t *out, void *stream);
 
 /* Measurement aid (bench.py; nothing on the product path calls it): the rate this device
  * sustains for the access shapes of K2 and K3 on the CALLER's buffer, so that the ceilings the

@@ -28,7 +28,8 @@ SYMBOLS = ("n2v_abi_version", "n2v_status_string", "n2v_device_count", "n2v_alia
            "n2v_delta_reduce", "n2v_wedge_slots_build", "n2v_sgns_job_alpha", "n2v_rank_hops_build", "n2v_partition_forward",
            "n2v_sgns_hogwild_waves", "n2v_walk_weighted_step", "n2v_partition_forward_boxes", "n2v_walk_weighted_keys",
            "n2v_wedge_slots_fold", "n2v_edge_row_sums_build", "n2v_knn_inv_norms", "n2v_knn_workspace_bytes",
-           "n2v_knn_topk", "n2v_knn_scores", "n2v_hs_tree_build", "n2v_hs_train", "n2v_hs_hogwild_waves")
+           "n2v_knn_topk", "n2v_knn_scores", "n2v_hs_tree_build", "n2v_hs_train", "n2v_hs_hogwild_waves",
+           "n2v_rank_pairs_build")
 
 
 class WeightedHubs(C.Structure):
@@ -131,6 +132,8 @@ def load():
     L.n2v_rank_hops_build.restype = C.c_int
     L.n2v_rank_hops_build.argtypes = [C.POINTER(Graph), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]
+    L.n2v_rank_pairs_build.restype = C.c_int
+    L.n2v_rank_pairs_build.argtypes = L.n2v_rank_hops_build.argtypes
     L.n2v_pivots_build.restype = C.c_int
     L.n2v_pivots_build.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.n2v_walk.restype = C.c_int

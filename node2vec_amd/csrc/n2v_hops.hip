@@ -120,10 +120,20 @@ extern "C" int n2v_hops_build(const n2v_graph *g, n2v_hop *hops_out, uint32_t *s
 namespace n2v {
 // One wave per 64 consecutive ranks (neighbouring ranks have neighbouring degrees): rows of 64
 // entries or more are copied by the whole wave one after the other, shorter ones lane per row.
+// Entry = uint32_t: the neighbour's rank (n2v_rank_hops_build); uint64_t: its rank << 32 | its vertex id
+// (n2v_rank_pairs_build).
+template <typename Entry>
+__device__ __forceinline__ Entry rank_entry(const int32_t *__restrict__ rank_of, int32_t c) {
+  const uint32_t rk = (uint32_t)rank_of[c];
+  if (sizeof(Entry) == 8) return (Entry)(((uint64_t)rk << 32) | (uint64_t)(uint32_t)c);
+  return (Entry)rk;
+}
+
+template <typename Entry>
 __global__ __launch_bounds__(256) void rank_hops_build_kernel(n2v_graph g, const int32_t *__restrict__ rank_of,
                                                               const int32_t *__restrict__ rank_vertex,
                                                               const int64_t *__restrict__ rank_rowptr,
-                                                              uint32_t *__restrict__ out) {
+                                                              Entry *__restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int64_t n_waves = (int64_t)gridDim.x * (blockDim.x >> 6);
   const int64_t groups = (g.n_vertices + 63) >> 6;
@@ -143,26 +153,38 @@ __global__ __launch_bounds__(256) void rank_hops_build_kernel(n2v_graph g, const
       big &= big - 1;
       const int64_t s_src = __shfl(src, l, 64), s_dst = __shfl(dst, l, 64);
       const int s_d = __shfl(d, l, 64);
-      for (int k = lane; k < s_d; k += 64) out[s_dst + k] = (uint32_t)rank_of[g.col[s_src + k]];
+      for (int k = lane; k < s_d; k += 64) out[s_dst + k] = rank_entry<Entry>(rank_of, g.col[s_src + k]);
     }
     if (d < 64)
-      for (int k = 0; k < d; ++k) out[dst + k] = (uint32_t)rank_of[g.col[src + k]];
+      for (int k = 0; k < d; ++k) out[dst + k] = rank_entry<Entry>(rank_of, g.col[src + k]);
   }
 }
-}  // namespace n2v
 
-extern "C" int n2v_rank_hops_build(const n2v_graph *g, const int32_t *rank_of, const int32_t *rank_vertex,
-                                   const int64_t *rank_rowptr, uint32_t *out, void *stream) {
+template <typename Entry>
+static int rank_table_build(const n2v_graph *g, const int32_t *rank_of, const int32_t *rank_vertex,
+                            const int64_t *rank_rowptr, Entry *out, void *stream) {
   if (!g || !g->rowptr || g->n_vertices < 0 || g->n_edges < 0) return N2V_EINVAL;
   if (g->w || g->w64) return N2V_EINVAL;  // unit-weight graphs only
   if (g->n_edges >= (1ll << N2V_HOP_DEG_SHIFT) || g->n_vertices >= (1ll << 31)) return N2V_EINVAL;
   if (g->n_edges == 0) return N2V_OK;
   if (!g->col || !rank_of || !rank_vertex || !rank_rowptr || !out) return N2V_EINVAL;
   int64_t blocks = ((g->n_vertices + 63) / 64 + 3) / 4;
-  const int64_t cap = n2v::resident_blocks((const void *)n2v::rank_hops_build_kernel, 256, 0) * 4;
+  const int64_t cap = resident_blocks((const void *)rank_hops_build_kernel<Entry>, 256, 0) * 4;
   if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(n2v::rank_hops_build_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(rank_hops_build_kernel<Entry>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                      *g, rank_of, rank_vertex, rank_rowptr, out);
   N2V_HIP_CHECK(hipGetLastError());
   return N2V_OK;
+}
+}  // namespace n2v
+
+extern "C" int n2v_rank_hops_build(const n2v_graph *g, const int32_t *rank_of, const int32_t *rank_vertex,
+                                   const int64_t *rank_rowptr, uint32_t *out, void *stream) {
+  return n2v::rank_table_build<uint32_t>(g, rank_of, rank_vertex, rank_rowptr, out, stream);
+}
+
+// the same rows with 8-byte entries {vertex id, rank} (include/n2v_hip.h): the walk that writes vertex ids
+extern "C" int n2v_rank_pairs_build(const n2v_graph *g, const int32_t *rank_of, const int32_t *rank_vertex,
+                                    const int64_t *rank_rowptr, uint64_t *out, void *stream) {
+  return n2v::rank_table_build<uint64_t>(g, rank_of, rank_vertex, rank_rowptr, out, stream);
 }

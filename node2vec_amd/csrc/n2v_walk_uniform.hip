@@ -28,6 +28,12 @@
 //     offset(class) + (rank - first(class)) * degree(class), the class found by a 13-step search of
 //     an LDS table (the probe shows the search is free: 51.6 - 53.2 G/s).  The few top ranks whose
 //     degrees are all different are looked up in a small cached table instead.
+//   * the pair table (n2v_rank_pairs_build, n2v_graph.rank_emit == 2): the ranked form's frame with
+//     entries of 8 bytes, {vertex id, rank} of the neighbour.  The low word goes to the path as it is
+//     (vertex ids out without the second gather through rank_vertex that costs the 4-byte form a third
+//     of its rate), the high word gives the next row through the class search.  Half the bytes of a
+//     16-byte hop entry on any graph the ranked form accepts, no escape read: what serves vertex-id
+//     output where the field widths of the 8-byte hop table (hops8) do not fit the graph (cfg 4).
 // Same uniform stream as every other kernel (step_bits, n2v_common.h): bit-identical walks.
 #include "n2v_common.h"
 
@@ -57,7 +63,8 @@ __device__ __forceinline__ void rank_row(const n2v_graph &g, const uint32_t *fir
 // kHops: 0 = CSR arrays (two gathers per step), 1 = the 16-byte hop table, 2 = the 8-byte hop
 // table (round 3: the chip serves 8-byte gathers over a table half the size a quarter faster),
 // 3 = the degree-ranked 4-byte table (blocks of 1024 threads, the class table in LDS: up to 8191
-// classes in 64 KB, two blocks per CU)
+// classes in 64 KB, two blocks per CU), 4 = the same frame on the 8-byte {vertex id, rank} pair table
+// (g.rank_hops points at uint64 entries; vertex ids out)
 template <int kHops, int kThreads>
 __global__ __launch_bounds__(kThreads, 8) void walk_uniform_kernel(
     n2v_graph g, const int32_t *__restrict__ start_ids, int64_t n_start, int32_t num_walks,
@@ -70,8 +77,8 @@ __global__ __launch_bounds__(kThreads, 8) void walk_uniform_kernel(
   const bool base_aligned = (reinterpret_cast<uintptr_t>(walks_out) & 63u) == 0;
   extern __shared__ uint32_t rank_lds[];
   const uint32_t *cls_first = rank_lds;
-  const uint32_t *cls_where = rank_lds + (kHops == 3 ? g.rank_classes : 0);
-  if (kHops == 3) {
+  const uint32_t *cls_where = rank_lds + (kHops >= 3 ? g.rank_classes : 0);
+  if (kHops >= 3) {
     for (int c = threadIdx.x; c < g.rank_classes; c += kThreads) {
       rank_lds[c] = g.rank_class_first[c];
       rank_lds[g.rank_classes + c] = g.rank_class_off[c];
@@ -101,7 +108,7 @@ __global__ __launch_bounds__(kThreads, 8) void walk_uniform_kernel(
     int64_t vb = 0;
     int n = 0;
     int32_t v_emit = v;
-    if (kHops == 3) {
+    if (kHops >= 3) {
       if (alive) {
         const int32_t rk = g.rank_of[v];
         if (emit_rank) v_emit = rk;
@@ -155,7 +162,11 @@ __global__ __launch_bounds__(kThreads, 8) void walk_uniform_kernel(
       if (walking) {
         const uint64_t bits = step_bits(h0, (uint32_t)step);
         const int pick = pick_index((uint32_t)(bits >> 32), n);  // int(r1 * n); r2 is irrelevant
-        if (kHops == 3) {
+        if (kHops == 4) {
+          const uint64_t e = reinterpret_cast<const uint64_t *>(g.rank_hops)[vb + pick];
+          x = (int32_t)(uint32_t)e;  // the neighbour's vertex id; its rank names the next row
+          if (step + 1 < walk_length) rank_row(g, cls_first, cls_where, (uint32_t)(e >> 32), vb, n);
+        } else if (kHops == 3) {
 #if defined(N2V_ABLATE_UNIFORM) && N2V_ABLATE_UNIFORM == 2  // timing only: no table read (placement diagnosis)
           const uint32_t xr = (uint32_t)((bits >> 7) % (uint64_t)g.n_vertices);
 #else
@@ -211,32 +222,44 @@ extern "C" int n2v_walk_uniform_try(const n2v_graph *g, const int32_t *start_ids
   const int64_t total = n_start * (int64_t)num_walks;
   if (total >= 0xffffff00ll) return 0;
   if (total == 0) return 1;
-  // status[1] is the kernel's walker counter: start it at zero on the same stream
-  if (hipMemsetAsync(status + 1, 0, sizeof(uint32_t), (hipStream_t)stream) != hipSuccess)
-    return N2V_ELAUNCH;
-  int64_t blocks = (total + 255) / 256;
-  const int form = g->rank_hops ? 3 : g->hops8 ? 2 : (g->hops ? 1 : 0);
-  if (form == 3) {
+  // which table serves, and its argument checks: before anything is put on the stream.  rank_emit says what
+  // rank_hops points at: 0 / 1 the 4-byte ranks (vertex ids / ranks out), 2 the 8-byte {id, rank} pairs
+  const int form = g->rank_hops ? (g->rank_emit == 2 ? 4 : 3) : g->hops8 ? 2 : (g->hops ? 1 : 0);
+  if (form >= 3) {
     const int P = g->rank_classes;
     if (P < 2 || P > 8192 || (P & (P - 1)) || !g->rank_of || !g->rank_class_first || !g->rank_class_off ||
         g->n_edges >= (1ll << 32) ||
         g->rank_head_n < 0 || g->rank_head_n > (1 << 22) || (g->rank_head_n > 0 && !g->rank_head) ||
-        (g->rank_emit == 0 && !g->rank_vertex) || (g->rank_emit & ~1))
+        (g->rank_emit == 0 && !g->rank_vertex) || g->rank_emit < 0 || g->rank_emit > 2)
       return N2V_EINVAL;
-    const size_t lds = (size_t)P * 8;
-    blocks = (total + 1023) / 1024;
-    const int64_t cap3 = n2v::resident_blocks((const void *)n2v::walk_uniform_kernel<3, 1024>, 1024, lds);
-    if (blocks > cap3) blocks = cap3;
-    hipLaunchKernelGGL((n2v::walk_uniform_kernel<3, 1024>), dim3((unsigned)blocks), dim3(1024), lds,
-                       (hipStream_t)stream, *g, start_ids, n_start, num_walks, walk_length, seed, walks_out,
-                       valid_out, status);
-    if (hipGetLastError() != hipSuccess) return N2V_ELAUNCH;
-    return 1;
   }
   if (form == 2 && (g->hop8_col_bits < 1 || g->hop8_row_bits < 1 ||
                     g->hop8_col_bits + g->hop8_row_bits > 62 || g->hop8_align_shift < 0 ||
                     g->hop8_align_shift > 6 || (g->hop8_align_shift > 0 && !g->hop8_rowptr)))
     return N2V_EINVAL;
+  // status[1] is the kernel's walker counter: start it at zero on the same stream
+  if (hipMemsetAsync(status + 1, 0, sizeof(uint32_t), (hipStream_t)stream) != hipSuccess)
+    return N2V_ELAUNCH;
+  int64_t blocks = (total + 255) / 256;
+  if (form >= 3) {
+    const size_t lds = (size_t)g->rank_classes * 8;
+    const void *fn3 = form == 4 ? (const void *)n2v::walk_uniform_kernel<4, 1024>
+                                : (const void *)n2v::walk_uniform_kernel<3, 1024>;
+    blocks = (total + 1023) / 1024;
+    const int64_t cap3 = n2v::resident_blocks(fn3, 1024, lds);
+    if (blocks > cap3) blocks = cap3;
+#define N2V_RANKED_LAUNCH(F)                                                                          \
+  hipLaunchKernelGGL((n2v::walk_uniform_kernel<F, 1024>), dim3((unsigned)blocks), dim3(1024), lds,    \
+                     (hipStream_t)stream, *g, start_ids, n_start, num_walks, walk_length, seed,       \
+                     walks_out, valid_out, status)
+    if (form == 4)
+      N2V_RANKED_LAUNCH(4);
+    else
+      N2V_RANKED_LAUNCH(3);
+#undef N2V_RANKED_LAUNCH
+    if (hipGetLastError() != hipSuccess) return N2V_ELAUNCH;
+    return 1;
+  }
   const void *fn = form == 2   ? (const void *)n2v::walk_uniform_kernel<2, 256>
                    : form == 1 ? (const void *)n2v::walk_uniform_kernel<1, 256>
                                : (const void *)n2v::walk_uniform_kernel<0, 256>;

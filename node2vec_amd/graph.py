@@ -101,6 +101,10 @@ class DeviceGraph:
         self.rank_class_first: Optional[torch.Tensor] = None  # int32 [P] (uint32)
         self.rank_class_off: Optional[torch.Tensor] = None  # int32 [P] (uint32)
         self.rank_tried = False
+        # the pair table (build_rank_pairs): 8-byte {vertex id, rank} entries in the ranked layout, for p = q = 1
+        # walks that write vertex ids; shares rank_of, the head and the class tables with the ranked form
+        self.rank_pairs: Optional[torch.Tensor] = None  # int64 [E]: rank << 32 | vertex id
+        self.rank_pairs_tried = False
         # caches of the weighted step kernels (randomwalk.weighted_row_sums, weighted_hub_summaries,
         # _walk_weighted_lanes): functions of rowptr / the stored weights alone.  `w` has no setter and
         # the arrays of a DeviceGraph are never replaced in place, so they cannot go stale.
@@ -197,7 +201,7 @@ class DeviceGraph:
                         None if self._w is None else self._w.to(device))
         for name in ("slots", "pivots", "edge_classes", "hops", "hops8", "hops8_rowptr", "wedge_off",
                      "wedge_pos", "wedge_slots", "rank_hops", "rank_of", "rank_vertex", "rank_head",
-                     "rank_class_first", "rank_class_off"):
+                     "rank_class_first", "rank_class_off", "rank_pairs"):
             t = getattr(self, name)
             if t is not None:
                 setattr(g, name, t.to(device))
@@ -205,6 +209,7 @@ class DeviceGraph:
         g.hops8_bits, g.hops8_shift = self.hops8_bits, self.hops8_shift
         # a declined build (escape share, memory budget) stays declined on the copy
         g.hops8_tried, g.wedge_tried, g.rank_tried = self.hops8_tried, self.wedge_tried, self.rank_tried
+        g.rank_pairs_tried = self.rank_pairs_tried
         g.hops_inline_rpos = self.hops_inline_rpos
         g.wedge_mode = self.wedge_mode
         g.slots_folded = self.slots_folded
@@ -275,9 +280,12 @@ class DeviceGraph:
         return self
 
     def _rank_fields(self):
-        if self.rank_hops is None:
+        # (the rank tables without rank_hops -- a graph that has the pair table alone -- mean nothing to a
+        # kernel until randomwalk.walk points rank_hops at the pairs and sets rank_emit = 2)
+        if self.rank_of is None or self.rank_vertex is None or self.rank_class_first is None:
             return (0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
-        return (self.rank_hops.data_ptr(), self.rank_of.data_ptr(), self.rank_vertex.data_ptr(),
+        return (0 if self.rank_hops is None else self.rank_hops.data_ptr(), self.rank_of.data_ptr(),
+                self.rank_vertex.data_ptr(),
                 0 if self.rank_head is None else self.rank_head.data_ptr(),
                 self.rank_class_first.data_ptr(), self.rank_class_off.data_ptr(),
                 0 if self.rank_head is None else self.rank_head.numel(), self.rank_class_first.numel(), 0, 0)
@@ -618,6 +626,53 @@ class DeviceGraph:
         self.rank_of, self.rank_vertex, self.rank_head = rank_of, rank_vertex, head
         self.rank_class_first, self.rank_class_off = first, off
         self.rank_hops = hops
+        return self
+
+    def build_rank_pairs(self, max_bytes: Optional[int] = None) -> "DeviceGraph":
+        """The pair table for p = q = 1 walks on unit weights that write VERTEX IDS (n2v_rank_pairs_build): the
+        rows of the degree-ranked form with 8-byte entries, the neighbour's rank << 32 | its vertex id.  A step
+        is one 8-byte gather -- the id goes to the path, the rank names the next row through the class table --
+        on any graph the ranked form accepts, whatever its field widths (the 8-byte hop table of build_hops8
+        needs id + row start + degree in 64 bits and is declined on cfg 4).  8 bytes per edge; rank_of, the
+        head and the class tables are the ranked form's (computed here when the graph does not have them
+        yet; the 4-byte rank_hops is neither built nor touched).  Declined (rank_pairs stays None) where
+        build_ranked declines, and when the table does not fit in `max_bytes` (default: half of the free
+        device memory)."""
+        L = _lib.load()
+        _lib.require_gpu()
+        self.rank_pairs_tried = True
+        self.rank_pairs = None
+        if not self.unit_weights or not self.rowptr.is_cuda:
+            return self
+        n, dev = self.n_vertices, self.device
+        deg = self.degrees()
+        if (self.n_edges == 0 or self.n_edges >= (1 << 32) or n >= (1 << 31)
+                or int(deg.max()) >= self.HOP_MAX_DEGREE):
+            return self
+        if max_bytes is None:
+            max_bytes = torch.cuda.mem_get_info(dev)[0] // 2
+        have = self.rank_of is not None and self.rank_vertex is not None and self.rank_class_first is not None
+        # (the tables' temporaries while they are computed: two sorts' worth of int64 per vertex)
+        if 8 * self.n_edges + (0 if have else 48 * n) > max_bytes:
+            return self
+        if have:
+            rank_of, rank_vertex = self.rank_of, self.rank_vertex
+            rank_rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(deg[rank_vertex.long()], 0, out=rank_rowptr[1:])
+        else:
+            tables = rank_tables(deg, self.RANK_MAX_CLASSES, self.RANK_MAX_HEAD)
+            if tables is None:
+                return self
+            rank_vertex, rank_of, rank_rowptr, head, first, off = tables
+        pairs = torch.empty(self.n_edges, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.n2v_rank_pairs_build(self.c_struct(), rank_of.data_ptr(), rank_vertex.data_ptr(),
+                                              rank_rowptr.data_ptr(), pairs.data_ptr(),
+                                              _lib.current_stream_ptr()), "n2v_rank_pairs_build")
+        if not have:
+            self.rank_of, self.rank_vertex, self.rank_head = rank_of, rank_vertex, head
+            self.rank_class_first, self.rank_class_off = first, off
+        self.rank_pairs = pairs
         return self
 
     def build_pivots(self) -> "DeviceGraph":

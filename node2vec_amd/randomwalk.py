@@ -71,7 +71,8 @@ def walk(graph: DeviceGraph, start_ids: torch.Tensor, num_walks: int, walk_lengt
          stats: Optional[dict] = None, use_edge_classes: bool = True, use_hops: bool = True,
          use_wedges: bool = True, use_wedge_kernel: bool = True, use_hops8: bool = True,
          use_workspace: bool = False, use_wedge_slots: bool = True, use_ranked: Optional[bool] = None,
-         rank_ids: bool = False, use_weighted_lanes: Optional[bool] = None, use_row_sums: bool = True):
+         rank_ids: bool = False, use_weighted_lanes: Optional[bool] = None, use_row_sums: bool = True,
+         use_rank_pairs: bool = True):
     """Launch K2.  Returns (walks int32 [n_start*num_walks, walk_length+1], valid bool).
 
     mode "fast", and on weighted graphs mode "exact" with return_param == inout_param == 1
@@ -91,7 +92,13 @@ def walk(graph: DeviceGraph, start_ids: torch.Tensor, num_walks: int, walk_lengt
     closed forms in the main launches, the ~1 % of steps they decline replayed out of line;
     64 bytes per walker, allocated here); use_workspace=False keeps the one-launch kernel: same
     bits.
-    Exact p = q = 1 walks on unit weights can run on the degree-ranked form (graph.build_ranked():
+    Exact p = q = 1 walks on unit weights need no class counts, and an entry of 8 bytes is enough for a step:
+    the 8-byte hop table where the graph's field widths allow it (graph.build_hops8()), else the pair table
+    (graph.build_rank_pairs(): {vertex id, degree rank} of the neighbour, rows in rank order -- any graph the
+    ranked form accepts), else the 16-byte hop table; each is built on first use and the 16-byte table is
+    not built for such a walk when a narrower one serves.  use_hops8=False asks for the 16-byte table,
+    use_rank_pairs=False keeps the pair table alone out of the way: same bits.
+    They can also run on the degree-ranked form (graph.build_ranked():
     4-byte entries, the neighbour's RANK by descending degree).  rank_ids=True returns the walks in
     ranks (map with graph.rank_vertex, or compose it into the per-token lookup that follows, as
     fit_streaming does): the form is built on first use and one step is one 4-byte gather.  With
@@ -169,7 +176,7 @@ def walk(graph: DeviceGraph, start_ids: torch.Tensor, num_walks: int, walk_lengt
     if rank_ids and not ranked:
         raise ValueError("rank_ids: exact p = q = 1 walks on a unit-weight graph that has a degree-ranked "
                          "form (graph.build_ranked()) only")
-    uniform8 = False
+    uniform8 = pairs = False
     if ranked:
         pass
     elif graph.unit_weights and use_hops and use_hops8 and not biased and mode == "exact":
@@ -178,7 +185,15 @@ def walk(graph: DeviceGraph, start_ids: torch.Tensor, num_walks: int, walk_lengt
         if graph.hops8 is None and not graph.hops8_tried:
             graph.build_hops8()
         uniform8 = graph.hops8 is not None
-    if graph.unit_weights and use_hops and not uniform8 and not ranked:
+        if not uniform8 and use_rank_pairs:
+            # declined (cfg 4: 27-bit ids leave no room for the degree): 8-byte {vertex id, rank} entries in
+            # the degree-ranked layout carry a step on any graph that form accepts
+            if graph.rank_pairs is not None and graph.rank_of is None:
+                graph.rank_pairs = None  # (the rank tables it is read with were dropped)
+            if graph.rank_pairs is None and not graph.rank_pairs_tried:
+                graph.build_rank_pairs()
+            pairs = graph.rank_pairs is not None
+    if graph.unit_weights and use_hops and not uniform8 and not ranked and not pairs:
         # hop table (16 bytes per edge): one gather per step instead of two or three.  It embeds
         # the class counts, so it is (re)built after them when a biased walk first needs them.
         want_classes = graph.edge_classes is not None
@@ -220,6 +235,9 @@ def walk(graph: DeviceGraph, start_ids: torch.Tensor, num_walks: int, walk_lengt
     if not ranked:
         g.rank_hops = 0
     g.rank_emit = 1 if rank_ids else 0
+    if pairs:  # the ranked kernel's frame on the pair table: vertex ids out, no second gather
+        g.rank_hops = graph.rank_pairs.data_ptr()
+        g.rank_emit = 2
     if not use_wedges or not use_edge_classes:
         g.wedge_off = 0
         g.wedge_pos = 0
