@@ -1,0 +1,179 @@
+"""Corpora on which the racy (hogwild) trainers are schedule-independent, and the proof that they are.
+
+Both word2vec updates skip a node or target whose f <= -6 or f >= 6 BEFORE any store.  So a launch of
+many unsynchronised waves computes exactly what one thread computes when
+  * no two sentences train the same row, and
+  * the rows every sentence must read (HS: the top of the tree; SGNS: the negative samples) are
+    saturated, so nobody ever writes them.
+`prove` checks those conditions under the CPU restatement alone; only then is a GPU comparison with
+the restatement's joint run meaningful (tests/test_train_geometry_cpu.py, test_train_geometry_gpu.py).
+
+Not a test module: helpers shared by the two.
+"""
+import numpy as np
+
+V_WORDS = 1024            # words that occur in sentences: 32 waves by the library's rule n_vocab / 32
+TOKENS = 40               # tokens per sentence
+WINDOW = 5
+NEGATIVE = 5
+SEED = 5
+SATURATED = 8.0           # f = 8 * syn0[., 0] at a shared row; syn0[., 0] stays far above 6 / 8
+# launches of one case: sentence_base moves on by the number of rows, the rate falls
+ALPHAS = (0.025, 0.02, 0.015)
+
+
+class Case:
+    """one corpus and model: numpy matrices, and `run(walks, m0, m1, base, alpha) -> pairs`, the CPU
+    restatement training `walks` in place on (m0, m1) with sentence ids base, base + 1, ..."""
+
+    def __init__(self, name, dim, walks, m0, m1, shared, run, extra=None):
+        self.name, self.dim, self.walks, self.m0, self.m1 = name, dim, walks, m0, m1
+        self.shared = np.asarray(shared, np.int64)  # rows of m1 every sentence reads and nobody writes
+        self.run = run
+        self.extra = extra or {}
+
+    def launches(self):
+        rows = self.walks.shape[0]
+        return [(k * rows, a) for k, a in enumerate(ALPHAS)]
+
+
+def prove(case):
+    """The conditions of the module docstring, under the restatement alone.  Returns the joint run:
+    (m0, m1, pairs).  A case that fails here is a wrongly built case."""
+    walks = case.walks
+    j0, j1 = case.m0.copy(), case.m1.copy()
+    pairs = 0
+    for base, alpha in case.launches():
+        pairs += case.run(walks, j0, j1, base, alpha)
+    assert pairs > 0
+    # the shared rows keep their bits
+    assert np.array_equal(j1[case.shared].view(np.uint32), case.m1[case.shared].view(np.uint32)), \
+        "a shared row was written: it is not saturated"
+    # every sentence alone, from the initial state, under the sentence ids of the joint run
+    merged0, merged1 = case.m0.copy(), case.m1.copy()
+    touch0 = np.zeros(case.m0.shape[0], np.int64)
+    touch1 = np.zeros(case.m1.shape[0], np.int64)
+    alone = 0
+    for r in range(walks.shape[0]):
+        s0, s1 = case.m0.copy(), case.m1.copy()
+        for base, alpha in case.launches():
+            alone += case.run(walks[r:r + 1], s0, s1, base + r, alpha)  # n_walks = 1
+        c0 = (s0.view(np.uint32) != case.m0.view(np.uint32)).any(1)
+        c1 = (s1.view(np.uint32) != case.m1.view(np.uint32)).any(1)
+        touch0 += c0
+        touch1 += c1
+        merged0[c0] = s0[c0]
+        merged1[c1] = s1[c1]
+    assert touch0.max() <= 1 and touch1.max() <= 1, "a row is changed by two sentences"
+    assert not touch1[case.shared].any()
+    assert alone == pairs
+    assert np.array_equal(merged0.view(np.uint32), j0.view(np.uint32)), "merged per-sentence runs != joint run (syn0)"
+    assert np.array_equal(merged1.view(np.uint32), j1.view(np.uint32)), "merged per-sentence runs != joint run (syn1)"
+    # it trained, and widely: a vacuous case proves nothing
+    assert touch0.sum() > walks.shape[0] * 4 and touch1.sum() > walks.shape[0] * 4
+    return j0, j1, pairs
+
+
+def _sentences(rng, groups, oov):
+    walks = np.stack([rng.choice(g, TOKENS) for g in groups]).astype(np.int32)
+    if oov:  # out-of-vocabulary tokens: dropped before windowing
+        walks[rng.random(walks.shape) < 0.15] = -1
+        walks[0, :3] = -1
+        walks[-1, -2:] = -1
+    return walks
+
+
+def _syn0(rng, rows, dim, away_from_zero=False):
+    if away_from_zero:
+        # magnitudes in [0.5, 1) / dim with random signs (see sgns_case)
+        x = (0.5 + 0.5 * rng.random((rows, dim))) * rng.choice([-1.0, 1.0], (rows, dim)) / dim
+    else:
+        x = (rng.random((rows, dim)) - 0.5) / dim  # word2vec's initialisation
+    x = x.astype(np.float32)
+    x[:, 0] = 1.0
+    return x
+
+
+# ---- hierarchical softmax ------------------------------------------------------------------------------------
+
+def hs_tree():
+    """1024 words of equal count: CreateBinaryTree gives a complete tree of depth 10"""
+    from node2vec_amd import hs
+
+    tree = hs.build_tree(np.full(V_WORDS, 7, np.int64))
+    assert tree.lengths.min() == tree.lengths.max() == 10
+    return tree
+
+
+def hs_case(hs_cpu, dim, depth=5, oov=False, saturated=SATURATED):
+    """2^depth sentences; sentence s draws only from the words under the s-th node of depth `depth`.
+    The syn1 rows of depth < `depth` are [saturated, 0, ...]: with syn0[:, 0] = 1 their f is >= 6 and
+    they are never written.  Every other syn1 row is zero (Spark's initialisation) and lies on the paths
+    of one sentence's words only."""
+    from node2vec_amd import sgns
+
+    tree = hs_tree()
+    paths = np.ascontiguousarray(tree.points.reshape(V_WORDS, 10))
+    groups = {}
+    for w in range(V_WORDS):
+        groups.setdefault(int(paths[w, depth]), []).append(w)
+    assert len(groups) == 2 ** depth and {len(g) for g in groups.values()} == {V_WORDS >> depth}
+    shared = np.unique(paths[:, :depth])
+    assert shared.size == 2 ** depth - 1
+    rng = np.random.default_rng(1000 * dim + 10 * depth + int(oov))
+    m0 = _syn0(rng, V_WORDS, dim)
+    m1 = np.zeros((V_WORDS - 1, dim), np.float32)
+    m1[shared, 0] = saturated
+    walks = _sentences(rng, [groups[k] for k in sorted(groups)], oov)
+    pts, exp = np.ascontiguousarray(tree.points), sgns.exp_table()
+
+    def run(w, s0, s1, base, alpha):
+        w = np.ascontiguousarray(w, np.int32)
+        return int(hs_cpu.n2v_hs_cpu_train(w.ctypes.data, w.shape[0], w.shape[1], s0.ctypes.data, s1.ctypes.data,
+                                           tree.path_off.ctypes.data, pts.ctypes.data, tree.codes.ctypes.data,
+                                           exp.ctypes.data, V_WORDS, base, SEED, dim, WINDOW, float(alpha), None))
+
+    return Case(f"hs-{dim}-{depth}-{int(oov)}", dim, walks, m0, m1, shared, run, {"tree": tree})
+
+
+# ---- negative sampling ---------------------------------------------------------------------------------------
+
+SINK = 0  # the word that takes every negative draw and occurs in no sentence
+
+
+def sgns_cum_table():
+    """all the mass of the noise distribution on word 0: bisect_left(cum_table, x) is 0 for every draw"""
+    from node2vec_amd import sgns
+
+    return np.full(V_WORDS + 1, sgns.CUM_DOMAIN, np.int32)
+
+
+def sgns_case(oracle, dim, sentences=32, oov=False, saturated=SATURATED):
+    """`sentences` sentences over disjoint word sets (words 1 .. 1024 dealt out at random); every
+    negative is the sink word 0, whose syn1neg row [saturated, 0, ...] has f >= 6 against every syn0 row
+    (syn0[:, 0] = 1, and label-1 updates only raise it).  What trains is the label-1 pair: syn0[context]
+    and syn1neg[centre], both words of the same sentence.
+
+    The other syn0 elements have magnitudes in [0.5, 1) / dim.  With the window cache a context row
+    goes back to memory as an atomic add of (value now - value as loaded); on a row nobody else writes
+    that equals a store whenever the subtraction is exact, which Sterbenz's lemma gives while an element
+    moves by less than half of itself between load and write-back.  Here a syn0 element moves by at most
+    12 % of itself over a whole launch (measured under the oracle; test_train_geometry_cpu.py holds the
+    three launches together under 50 %), and a row stays cached for a few positions of one sentence."""
+    from node2vec_amd import sgns
+
+    n_vocab = V_WORDS + 1
+    rng = np.random.default_rng(2000 * dim + 10 * sentences + int(oov))
+    words = 1 + rng.permutation(V_WORDS)
+    groups = np.split(words, sentences)
+    m0 = _syn0(rng, n_vocab, dim, away_from_zero=True)
+    m1 = np.zeros((n_vocab, dim), np.float32)
+    m1[SINK, 0] = saturated
+    walks = _sentences(rng, groups, oov)
+    assert not (walks == SINK).any()
+    cum, exp = sgns_cum_table(), sgns.exp_table()
+
+    def run(w, s0, s1, base, alpha):
+        return oracle.sgns_train(w, s0, s1, cum, None, exp, n_vocab, base, SEED, dim, WINDOW, NEGATIVE, alpha)
+
+    return Case(f"sgns-{dim}-{sentences}-{int(oov)}", dim, walks, m0, m1, [SINK], run)

@@ -46,9 +46,10 @@ def _cpu_train(L, m, idx, s0, s1, base, alpha, row_alpha=None):
     t = m.tree
     pts = np.ascontiguousarray(t.points) if t.points.size else np.zeros(1, np.int32)
     ra = None if row_alpha is None else np.ascontiguousarray(row_alpha, np.float32)
+    exp = sgns.exp_table()  # held in a name: the address of a temporary would dangle during the call
     return L.n2v_hs_cpu_train(w.ctypes.data, w.shape[0], w.shape[1], s0.ctypes.data, s1.ctypes.data,
                               t.path_off.ctypes.data, pts.ctypes.data, t.codes.ctypes.data,
-                              sgns.exp_table().ctypes.data, len(m.vocab), base, m.seed, m.dim, m.window,
+                              exp.ctypes.data, len(m.vocab), base, m.seed, m.dim, m.window,
                               float(alpha), None if ra is None else ra.ctypes.data)
 
 
@@ -186,8 +187,9 @@ def test_offsets_past_2_31_elements(hs_cpu):
         codes[k] = t.codes[w]
     pts = np.asarray(pts, np.int32)
     cidx = np.vectorize(wmap.get)(idx.cpu().numpy()).astype(np.int32)
+    exp = sgns.exp_table()
     n = hs_cpu.n2v_hs_cpu_train(cidx.ctypes.data, cidx.shape[0], cidx.shape[1], s0.ctypes.data, s1.ctypes.data,
-                                off.ctypes.data, pts.ctypes.data, codes.ctypes.data, sgns.exp_table().ctypes.data,
+                                off.ctypes.data, pts.ctypes.data, codes.ctypes.data, exp.ctypes.data,
                                 len(words), 0, m.seed, dim, 5, 0.025, None)
     assert n == int(m.pairs.item()) > 0
     assert np.array_equal(m.syn0[words].cpu().numpy(), s0)
