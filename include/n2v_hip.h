@@ -879,6 +879,26 @@ int n2v_hs_train(const int32_t *walks, int64_t n_walks, int32_t walk_len, float 
  * a negative status for parameters it would refuse. */
 int64_t n2v_hs_hogwild_waves(const n2v_hs_params *P, int64_t n_walks, int32_t walk_len);
 
+/* CBOW (sg = 0) with negative sampling: what gensim.models.Word2Vec trains at the reference's call
+ * site embedding.py:126 when `negative` is set and `sg` is left at gensim's default 0 (gensim 3.8
+ * train_batch_cbow / fast_sentence_cbow_neg; DESIGN.md "CBOW").  Arguments, sentence preparation,
+ * launch geometry and pairs_out as n2v_sgns_train, on the same syn0 / syn1neg; pairs_out[0] grows by
+ * one per trained POSITION (a centre word with at least one context word).  The `negative` draws are
+ * made once per position.  cbow_mean 1: the context vectors are averaged (gensim's default), 0: summed
+ * and the error divided by their number.  deterministic != 0: one wave, rows in order, bit-identical
+ * to tests/cpu_cbow/n2v_cbow_cpu.c.  params->batched != 0, params->window_cache != 0, cbow_mean
+ * outside {0, 1} and everything n2v_sgns_train refuses are N2V_EINVAL before anything is launched;
+ * n_walks == 0 is N2V_OK. */
+int n2v_cbow_train(const int32_t *walks, int64_t n_walks, int32_t walk_len,
+                   float *syn0, float *syn1neg, const uint32_t *cum_table,
+                   const uint32_t *sample_int, const float *exp_table,
+                   const n2v_sgns_params *params_host, int32_t cbow_mean,
+                   unsigned long long *pairs_out, void *stream);
+
+/* The waves n2v_cbow_train keeps in flight for such a launch on this device (nothing is launched), or
+ * a negative status for parameters it would refuse. */
+int64_t n2v_cbow_hogwild_waves(const n2v_sgns_params *P, int64_t n_walks, int32_t walk_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,7 @@ SYMBOLS = ("n2v_abi_version", "n2v_status_string", "n2v_device_count", "n2v_alia
            "n2v_sgns_hogwild_waves", "n2v_walk_weighted_step", "n2v_partition_forward_boxes", "n2v_walk_weighted_keys",
            "n2v_wedge_slots_fold", "n2v_edge_row_sums_build", "n2v_knn_inv_norms", "n2v_knn_workspace_bytes",
            "n2v_knn_topk", "n2v_knn_scores", "n2v_hs_tree_build", "n2v_hs_train", "n2v_hs_hogwild_waves",
-           "n2v_rank_pairs_build")
+           "n2v_rank_pairs_build", "n2v_cbow_train", "n2v_cbow_hogwild_waves")
 
 
 class WeightedHubs(C.Structure):
@@ -231,6 +231,11 @@ def load():
                                C.c_void_p, C.c_void_p, C.POINTER(HsParams), C.c_void_p, C.c_void_p]
     L.n2v_hs_hogwild_waves.restype = C.c_int64
     L.n2v_hs_hogwild_waves.argtypes = [C.POINTER(HsParams), C.c_int64, C.c_int32]
+    L.n2v_cbow_train.restype = C.c_int
+    L.n2v_cbow_train.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.POINTER(SgnsParams), C.c_int32, C.c_void_p, C.c_void_p]
+    L.n2v_cbow_hogwild_waves.restype = C.c_int64
+    L.n2v_cbow_hogwild_waves.argtypes = [C.POINTER(SgnsParams), C.c_int64, C.c_int32]
     _lib = L
     return L
 

@@ -49,7 +49,8 @@ GENSIM_PARAMS: Dict[str, Any] = {
 # out: gensim's own defaults for the pass-through names, except sg/negative which
 # select the north-star's skip-gram negative-sampling objective.
 HIP_SGNS_PARAMS: Dict[str, Any] = {
-    "sg": 1,
+    "sg": 1,            # 0: CBOW (gensim's own default objective), trained by n2v_cbow_train
+    "cbow_mean": 1,     # sg = 0 only: 1 averages the context vectors (gensim's default), 0 sums them
     "hs": 0,
     "negative": 5,
     "sample": 1e-3,

@@ -11,8 +11,10 @@ package name only.
 
 The one behavioural decision (SURVEY.md finding 4): the reference's defaults
 (negative=0 with gensim's sg=0, hs=0) perform no weight updates at all; this
-trainer is skip-gram with negative sampling, so sg=1 and a missing/zero `negative`
-becomes 5 (constants.HIP_SGNS_PARAMS).  hs=1 / sg=0 are rejected with ValueError.
+trainer uses negative sampling, so a missing/zero `negative` becomes 5 and a missing `sg`
+means 1, skip-gram (constants.HIP_SGNS_PARAMS).  sg=0 trains CBOW with negative sampling,
+gensim's own default objective (csrc/n2v_cbow.hip; `cbow_mean` 1 or 0 as in gensim).  hs=1 is
+rejected with ValueError.
 """
 import logging
 import os
@@ -329,6 +331,18 @@ class HipW2V:
         return cls(KeyedVectors(d["tokens"], d["vectors"]), d["syn1neg"], d["params"], d["pairs"])
 
 
+def _check_objective(p: Dict[str, Any]) -> None:
+    """hs=1 is not trained by this class; sg=0 is CBOW, which has no batched variant"""
+    if p.get("hs", 0):
+        raise ValueError("the HIP trainer implements hs=0 (negative sampling): sg=1 skip-gram, sg=0 CBOW")
+    if p.get("sg", 1) not in (0, 1, False, True):
+        raise ValueError(f"sg must be 0 (CBOW) or 1 (skip-gram), not {p['sg']!r}")
+    if p.get("cbow_mean", 1) not in (0, 1, False, True):
+        raise ValueError(f"cbow_mean must be 0 (sum) or 1 (mean), not {p['cbow_mean']!r}")
+    if not p.get("sg", 1) and p.get("batched", False):
+        raise ValueError("batched is a skip-gram trainer: not available with sg=0 (CBOW)")
+
+
 class Node2VecHIP(Node2VecBase):
     """Drop-in for Node2VecGensim (embedding.py:70-178) on one MI355X."""
 
@@ -358,8 +372,7 @@ class Node2VecHIP(Node2VecBase):
             if vector_size < 32 or vector_size > 1024:  # :114-115
                 raise ValueError(f"Inappropriate vector dimension {vector_size}!")
             w2v_params["size"] = vector_size
-        if w2v_params.get("hs", 0) or not w2v_params.get("sg", 1):
-            raise ValueError("the HIP trainer implements sg=1, hs=0 (skip-gram, negative sampling)")
+        _check_objective(w2v_params)
         logging.info(f"__init__(): w2v params: {w2v_params}")
         self.w2v_params = w2v_params
 
@@ -406,7 +419,7 @@ class Node2VecHIP(Node2VecBase):
             raise RuntimeError("you must first build vocabulary before training the model")
         m = sgns.SgnsModel(vocab, int(p["size"]), int(p["window"]), negative, int(p["seed"]),
                            sample=float(p["sample"] or 0.0), ns_exponent=float(p["ns_exponent"]),
-                           device=dev)
+                           device=dev, sg=int(bool(p["sg"])), cbow_mean=int(p["cbow_mean"]))
         # opt-in, not gensim's sampling: w2v_params["batched"] = True shares the k negatives of a
         # centre position among its pairs (csrc/n2v_sgns_batched.hip; dim 64 / 128 / 256,
         # window <= 7, negative <= 15)
@@ -435,7 +448,7 @@ class Node2VecHIP(Node2VecBase):
                 deterministic=bool(p.get("deterministic", False)),
                 batch_words=None if split else int(p.get("batch_words") or 0) or None)
         torch.cuda.synchronize(dev)
-        p["negative"] = negative
+        p["negative"], p["sg"], p["cbow_mean"] = negative, m.sg, m.cbow_mean
         # what the trainer really ran with (hub_rows None = chosen from the corpus: recorded, so that a
         # parity run can pin it -- hub_rows = 0 is gensim's code as written)
         p["hub_rows"], p["hub_rows_auto"], p["hub_waves"] = m.hub_rows, m.hub_rows_auto, m.hub_waves

@@ -25,7 +25,7 @@ import torch
 from node2vec_amd import randomwalk as rw
 from node2vec_amd import sgns
 from node2vec_amd.constants import GENSIM_PARAMS, HIP_SGNS_PARAMS, NODE2VEC_PARAMS
-from node2vec_amd.embedding import HipW2V, KeyedVectors
+from node2vec_amd.embedding import HipW2V, KeyedVectors, _check_objective
 from node2vec_amd.graph import DeviceGraph
 
 
@@ -76,7 +76,7 @@ def fit_streaming(graph: DeviceGraph, n2v_params: Dict[str, Any], w2v_params: Di
     n2v_params / w2v_params take the reference's keys (NODE2VEC_PARAMS, GENSIM_PARAMS plus
     the pass-through names of HIP_SGNS_PARAMS); missing keys are filled in the caller's
     dicts as the reference does (fugue.py:120-122, embedding.py:105-107).  w2v_params["batched"]
-    selects the opt-in shared-negative trainer; "sync_every" / "sync_wire" the multi-GPU exchange;
+    selects the opt-in shared-negative trainer; "sg": 0 trains CBOW ("cbow_mean" as in gensim); "sync_every" / "sync_wire" the multi-GPU exchange;
     "deterministic" the one-wave reproducible mode (tests).
     `timings` (optional dict) receives the seconds spent walking and training."""
     import time
@@ -91,8 +91,7 @@ def fit_streaming(graph: DeviceGraph, n2v_params: Dict[str, Any], w2v_params: Di
         w2v_params.setdefault(k, v)
     p = dict(HIP_SGNS_PARAMS)
     p.update(w2v_params)
-    if p.get("hs", 0) or not p.get("sg", 1):
-        raise ValueError("the HIP trainer implements sg=1, hs=0 (skip-gram, negative sampling)")
+    _check_objective(p)
     negative = int(p["negative"]) if p["negative"] else int(HIP_SGNS_PARAMS["negative"])
     W, L = int(n2v_params["num_walks"]), int(n2v_params["walk_length"])
     pp, qq = float(n2v_params["return_param"]), float(n2v_params["inout_param"])
@@ -162,7 +161,7 @@ def fit_streaming(graph: DeviceGraph, n2v_params: Dict[str, Any], w2v_params: Di
     rows_rank_max = n_start_max * W  # rows of the largest shard: the sentence-id stride of a rank
     model = sgns.SgnsModel(vocab, int(p["size"]), int(p["window"]), negative, int(p["seed"] or seed),
                            sample=float(p["sample"] or 0.0), ns_exponent=float(p["ns_exponent"]),
-                           device=dev)
+                           device=dev, sg=int(bool(p["sg"])), cbow_mean=int(p["cbow_mean"]))
     model.batched = bool(p.get("batched", False))
     model.hub_rows = None if p.get("hub_rows") is None else int(p["hub_rows"])
     deterministic = bool(p.get("deterministic", False))
@@ -214,7 +213,7 @@ def fit_streaming(graph: DeviceGraph, n2v_params: Dict[str, Any], w2v_params: Di
     if timings is not None:
         timings.update(walk_s=t_walk, train_s=t_train, batches=n_batches, epochs=epochs,
                        rows_this_rank=n_start * W, world=world)
-    p["negative"] = negative
+    p["negative"], p["sg"], p["cbow_mean"] = negative, model.sg, model.cbow_mean
     # what the trainer really ran with (hub_rows None = chosen from the corpus: recorded)
     p["hub_rows"], p["hub_rows_auto"], p["hub_waves"] = model.hub_rows, model.hub_rows_auto, model.hub_waves
     if timings is not None:

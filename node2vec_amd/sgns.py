@@ -1,4 +1,5 @@
-"""Skip-gram negative-sampling trainer: host logic around the K3 kernel (n2v_sgns_train).
+"""Negative-sampling trainer: host logic around the K3 kernel (n2v_sgns_train, skip-gram) and the
+CBOW kernel (n2v_cbow_train, SgnsModel(sg=0)).
 
 What gensim.models.Word2Vec(sentences, sg=1, hs=0, negative=k) does around its
 Cython inner loop (the reference's call site is embedding.py:126; gensim itself is
@@ -142,8 +143,15 @@ class SgnsModel:
 
     def __init__(self, vocab: Vocab, dim: int, window: int, negative: int, seed: int,
                  sample: float = 0.0, ns_exponent: float = 0.75, device=None,
-                 use_cum_index: bool = True):
+                 use_cum_index: bool = True, sg: int = 1, cbow_mean: int = 1):
         device = device or vocab.ids.device
+        if sg not in (0, 1):
+            raise ValueError(f"sg must be 0 (CBOW) or 1 (skip-gram), not {sg!r}")
+        if cbow_mean not in (0, 1):
+            raise ValueError(f"cbow_mean must be 0 (sum) or 1 (mean), not {cbow_mean!r}")
+        # sg = 0: CBOW (gensim's default objective; n2v_cbow_train); cbow_mean 1 averages the context
+        # vectors, 0 sums them.  `pairs` then counts trained positions.
+        self.sg, self.cbow_mean = int(sg), int(cbow_mean)
         self.vocab, self.dim, self.window, self.negative = vocab, int(dim), int(window), int(negative)
         self.seed = int(seed) & (2 ** 64 - 1)
         n = len(vocab)
@@ -194,10 +202,12 @@ class SgnsModel:
         P = _lib.SgnsParams(len(self.vocab), 0, self.seed, self.dim, self.window, self.negative, 0.025, 0,
                             self.cum_index_bits, 0 if self.cum_index is None else self.cum_index.data_ptr(),
                             int(self.max_waves), 0, int(self.window_cache), 0, 0)
+        fn, name = ((L.n2v_sgns_hogwild_waves, "n2v_sgns_hogwild_waves") if self.sg else
+                    (L.n2v_cbow_hogwild_waves, "n2v_cbow_hogwild_waves"))
         with torch.cuda.device(self.syn0.device):
-            w = int(L.n2v_sgns_hogwild_waves(P, int(rows), int(length)))
+            w = int(fn(P, int(rows), int(length)))
         if w < 0:
-            _lib.check(w, "n2v_sgns_hogwild_waves")
+            _lib.check(w, name)
         return max(w, 1)
 
     def auto_hub_rows(self, rows: int = 1 << 30, length: int = 81) -> int:
@@ -236,6 +246,10 @@ class SgnsModel:
         return h if self.hub_share >= self.HUB_MIN_SHARE else 0
 
     def _hub_rows(self, rows: int, length: int) -> int:
+        if self.hub_rows is None and not self.sg:
+            # auto_hub_rows was fitted to skip-gram measurements and its row-hold formula does not
+            # describe CBOW: plain stores unless the caller names a value
+            self.hub_rows = 0
         if self.hub_rows is None:
             self.hub_rows = self.auto_hub_rows(rows, length)
             self.hub_rows_auto = True
@@ -253,6 +267,8 @@ class SgnsModel:
             raise TypeError("train_block wants a CUDA int32 [rows, len] tensor")
         if walks_idx.shape[1] > MAX_SENTENCE:
             raise ValueError(f"walks longer than {MAX_SENTENCE}: split rows first (split_rows)")
+        if not self.sg and self.batched:
+            raise ValueError("batched is a skip-gram trainer: not available with sg=0 (CBOW)")
         walks_idx = walks_idx.contiguous()
         row_alpha = None
         if sched is not None and walks_idx.shape[0] > 0:  # the rate of every row: that of its gensim job
@@ -268,6 +284,16 @@ class SgnsModel:
                             int(self.max_waves), int(bool(self.batched)), int(self.window_cache),
                             self._hub_rows(walks_idx.shape[0], walks_idx.shape[1]),
                             0 if row_alpha is None else row_alpha.data_ptr())
+        if not self.sg:
+            with torch.cuda.device(walks_idx.device):
+                rc = L.n2v_cbow_train(walks_idx.data_ptr(), walks_idx.shape[0], walks_idx.shape[1],
+                                      self.syn0.data_ptr(), self.syn1neg.data_ptr(),
+                                      self.cum_table.data_ptr(),
+                                      0 if self.sample_int is None else self.sample_int.data_ptr(),
+                                      self.exp_table.data_ptr(), P, self.cbow_mean, self.pairs.data_ptr(),
+                                      _lib.current_stream_ptr())
+            _lib.check(rc, "n2v_cbow_train")
+            return
         with torch.cuda.device(walks_idx.device):
             rc = L.n2v_sgns_train(walks_idx.data_ptr(), walks_idx.shape[0], walks_idx.shape[1],
                                   self.syn0.data_ptr(), self.syn1neg.data_ptr(),
