@@ -604,6 +604,8 @@ int n2v_sgns_train(const int32_t *walks, int64_t n_walks, int32_t walk_len,
  *   n2v_delta_apply  mean = wire_sum[i] / world                       (F32)
  *                         = ref_bf16[i] + wire_sum[i] / world         (BF16; ref := bf16(mean))
  *                    cur[i] += mean - before[i]
+ *   ("/ world" is one correctly rounded fp32 division by (float)world, never a product with
+ *   1 / world: the two differ for every world that is no power of two)
  *
  * so that updates made to cur while the collective was in flight survive.  With
  * before_out / before == NULL no snapshot is taken and apply stores cur[i] = mean exactly

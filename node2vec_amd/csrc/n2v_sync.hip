@@ -6,6 +6,9 @@
 // collectives a rank only needs
 //   pack   wire = what this rank contributes to the sum, `before` = a snapshot of the rows
 //   apply  rows += mean - before   (updates made while the collective was in flight stay)
+//          mean = sum / (float)world: ONE correctly rounded fp32 division, the operation the host
+//          form states (sgns.DeltaSync._apply); a product with 1 / world is another operation
+//          for every world that is no power of two and would part device and host replicas
 // `wire` is either the fp32 rows themselves (parameter averaging: no reference copy at all)
 // or bf16(row - ref) against a bf16 reference every rank shares (half the bytes on xGMI;
 // the mean of the replicas equals ref + mean(row - ref) for ANY shared ref, and the
@@ -62,16 +65,16 @@ __global__ __launch_bounds__(256) void delta_apply_kernel(float *__restrict__ cu
                                                          uint16_t *__restrict__ ref,
                                                          const float *__restrict__ before,
                                                          const void *__restrict__ wire_sum,
-                                                         float inv_world, int64_t n) {
+                                                         float world, int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     float mean;
     if constexpr (kBf16) {
       mean = bf16_bits_to_float(ref[i]) +
-             bf16_bits_to_float(reinterpret_cast<const uint16_t *>(wire_sum)[i]) * inv_world;
+             bf16_bits_to_float(reinterpret_cast<const uint16_t *>(wire_sum)[i]) / world;
       ref[i] = float_to_bf16_bits(mean);
     } else {
-      mean = reinterpret_cast<const float *>(wire_sum)[i] * inv_world;
+      mean = reinterpret_cast<const float *>(wire_sum)[i] / world;
     }
     cur[i] = before ? cur[i] + (mean - before[i]) : mean;
   }
@@ -157,15 +160,15 @@ extern "C" int n2v_delta_apply(float *cur, uint16_t *ref_bf16, const float *befo
   if (n == 0) return N2V_OK;
   if (!cur || !wire_sum || (wire_dtype == N2V_WIRE_BF16 && !ref_bf16)) return N2V_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const float inv = 1.0f / (float)world;
+  const float w = (float)world;  // divided by, not multiplied with its reciprocal (see the head of the file)
   if (wire_dtype == N2V_WIRE_BF16) {
     const int64_t blocks = n2v::stream_blocks(n, (const void *)n2v::delta_apply_kernel<true>);
     hipLaunchKernelGGL(n2v::delta_apply_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, cur,
-                       ref_bf16, before, wire_sum, inv, n);
+                       ref_bf16, before, wire_sum, w, n);
   } else {
     const int64_t blocks = n2v::stream_blocks(n, (const void *)n2v::delta_apply_kernel<false>);
     hipLaunchKernelGGL(n2v::delta_apply_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st,
-                       cur, ref_bf16, before, wire_sum, inv, n);
+                       cur, ref_bf16, before, wire_sum, w, n);
   }
   N2V_HIP_CHECK(hipGetLastError());
   return N2V_OK;

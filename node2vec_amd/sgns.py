@@ -445,6 +445,9 @@ class DeltaSync:
       all-reduce, apply), while the main stream keeps training; `apply` adds mean - snapshot,
       so what was trained meanwhile is kept.  finish() drains it and ends with one blocking
       exchange that leaves all replicas bit-identical.
+    * the mean is sum / world, ONE fp32 division, in the kernel (n2v_delta_apply) as in the host
+      form below -- not a product with 1 / world, which rounds differently for every world that
+      is no power of two.  Both forms are held bit for bit to tests/exchange_restatement.py.
     Every rank must call step() the same number of times (SgnsModel.train sees to that)."""
 
     def __init__(self, model_or_tensors, group=None, sync_every: Optional[int] = None,
@@ -542,7 +545,7 @@ class DeltaSync:
         else:
             flat = cur.reshape(-1)
             if ref is None:
-                mean = wire / self.world
+                mean = wire / self.world  # a true fp32 division, as in delta_apply_kernel
             else:
                 mean = ref.reshape(-1).float() + wire.float() / self.world
                 ref.reshape(-1).copy_(mean)

@@ -212,6 +212,81 @@ def test_delta_all_reduce_and_sharding_world2():
     assert dict(ret) == {0: True, 1: True}
 
 
+_ROUNDS, _ADD_ROUND = 4, 2  # set, set, add, set: the run ends on a blocking exchange, with identical replicas
+
+
+def _trained(rank, round_):
+    """what rank `rank` adds to its two matrices before exchange `round_` (the same in worker and parent)"""
+    g = torch.Generator().manual_seed(1000 * round_ + rank)
+    scale = 10.0 ** (rank % 3 - 2)  # the ranks move by different magnitudes: the order of the sum shows
+    return [scale * torch.randn(37, 8, generator=g), scale * torch.randn(5, 3, generator=g)]
+
+
+def _delta_worker(rank, world, port, ret):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from node2vec_amd.sgns import DeltaSync
+
+        out = {}
+        for wire in ("fp32", "bf16"):
+            g = torch.Generator().manual_seed(5)
+            mats = [torch.randn(37, 8, generator=g), torch.randn(5, 3, generator=g)]  # same on every rank
+            sync = DeltaSync(mats, block_rows=16, sync_every=1, wire=wire)
+            states = []
+            for round_ in range(_ROUNDS):
+                for m, d in zip(mats, _trained(rank, round_)):
+                    m += d
+                if round_ != _ADD_ROUND:
+                    sync.step()  # on host tensors: a blocking exchange, rows SET to the mean
+                else:
+                    sync._exchange(exact=False)  # the overlapped form: mean - snapshot ADDED
+                states.append(([m.numpy().copy() for m in mats],
+                               None if sync.refs is None else
+                               [r.view(torch.int16).numpy().view(np.uint16).copy() for r in sync.refs]))
+            out[wire] = states
+        ret[rank] = out
+    finally:
+        dist.destroy_process_group()
+
+
+def test_delta_sync_world3_equals_the_restatement():
+    """three gloo ranks on host tensors: a mean over a world that is no power of two, where sum / 3 and
+    sum * (1 / 3) part ways.  Expected bits from tests/exchange_restatement.py; every rank ends identical.
+    (Its own worker: _worker above states a world of two throughout -- two shards, two mailboxes, a mean of
+    two -- and stays as it is.)"""
+    import exchange_restatement as R
+
+    world = 3
+    port = _free_port()
+    mgr = mp.Manager()
+    ret = mgr.dict()
+    mp.spawn(_delta_worker, args=(world, port, ret), nprocs=world, join=True)
+    got = dict(ret)
+    assert sorted(got) == [0, 1, 2]
+    for wire in ("fp32", "bf16"):
+        g = torch.Generator().manual_seed(5)
+        base = [torch.randn(37, 8, generator=g).numpy(), torch.randn(5, 3, generator=g).numpy()]
+        replicas = [[b.copy() for b in base] for _ in range(world)]
+        refs = None if wire == "fp32" else [[R.ref_init(b) for b in base] for _ in range(world)]
+        for round_ in range(_ROUNDS):
+            for r in range(world):
+                replicas[r] = [m + d.numpy() for m, d in zip(replicas[r], _trained(r, round_))]  # one fp32 add
+            replicas, refs = R.exchange(replicas, refs, 16, exact=round_ != _ADD_ROUND)
+            for r in range(world):
+                mats, rf = got[r][wire][round_]
+                for k in range(2):
+                    R.assert_same_bits(mats[k], replicas[r][k], f"{wire} round {round_} rank {r} matrix {k}")
+                    if refs is not None:
+                        R.assert_same_bits(rf[k], refs[r][k], f"{wire} round {round_} rank {r} reference {k}")
+                    if round_ != _ADD_ROUND:  # (the add form keeps each rank's own rounding of cur + (mean - before))
+                        R.assert_same_bits(mats[k], got[0][wire][round_][0][k], "identical replicas")
+                        if refs is not None:
+                            R.assert_same_bits(rf[k], got[0][wire][round_][1][k], "identical references")
+        assert len(got[0][wire]) == _ROUNDS and _ROUNDS - 1 != _ADD_ROUND  # the last state checked is a set one
+
+
 def test_delta_sync_is_identity_on_one_rank():
     from node2vec_amd.sgns import DeltaSync
 
