@@ -731,7 +731,11 @@ int n2v_partition_group(const int32_t *dest, const int64_t *head, int32_t head_c
  * travel this way.  The next n2v_partition_step takes mailbox d as head = box_head[d] / src_ptr =
  * box_off[d] / src_ids = box_words[d] with src_kind N2V_SRC_WEDGES_AT.  Replaces n2v_partition_route +
  * n2v_partition_group + a prefix sum + n2v_gather_wedges and the host read between them; the order
- * of the walkers in a mailbox is not defined, the walks are (the RNG is keyed by walker and step). */
+ * of the walkers in a mailbox is not defined, the walks are (the RNG is keyed by walker and step).
+ *   wide: the width of a UNIFORM wedge table only -- 0: every list uint16, 1: every list uint32; any other value
+ *   is N2V_EINVAL before anything is launched, here, in n2v_partition_forward_boxes and in n2v_gather_wedges.  A
+ *   mixed table (n2v_wedge_build with wide = T >= 2, n2v_graph.wedge_wide of such a graph) cannot be cut by edge
+ *   ranges: it is rebuilt with 32-bit lists throughout (wide = 1) first, as partition_graph does. */
 int n2v_partition_forward(const int64_t *head_in, int32_t head_cols, const int32_t *next,
                           const int64_t *edge, int64_t k, int32_t walk_length, const int64_t *bounds,
                           int32_t n_parts, int32_t carry, const uint32_t *edge_classes,

@@ -293,6 +293,7 @@ extern "C" int n2v_gather_wedges(const uint32_t *edge_classes, const uint64_t *w
                                  const int64_t *out_ptr, int64_t k, int32_t *out, int64_t *head,
                                  int32_t head_cols, void *stream) {
   if (k < 0 || head_cols < 5) return N2V_EINVAL;
+  if (wide != 0 && wide != 1) return N2V_EINVAL;  // a uniform table only (a mixed one: rebuilt with 32-bit lists)
   if (k == 0) return N2V_OK;
   if (!edge_classes || !wedge_off || !wedge_pos || !edges || !out_ptr || !out || !head)
     return N2V_EINVAL;
@@ -487,6 +488,7 @@ static int partition_forward(const int64_t *head_in, int32_t head_cols, const in
     return N2V_EINVAL;
   if (carry != 0 && carry != N2V_SRC_WEDGES + 1 && carry != N2V_SRC_WEDGES + 2) return N2V_EINVAL;
   if (carry != 0 && head_cols < 5) return N2V_EINVAL;
+  if (wide != 0 && wide != 1) return N2V_EINVAL;  // a uniform table only (a mixed one: rebuilt with 32-bit lists)
   if (k == 0) return N2V_OK;
   if (!head_in || !next || !bounds || !box_head || !box_off || !box_count || !status) return N2V_EINVAL;
   if (!log_out && (!walks_out || !valid_out)) return N2V_EINVAL;

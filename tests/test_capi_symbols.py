@@ -108,9 +108,9 @@ def test_partition_entry_points_validate_their_arguments():
                                        a["cap"], a["wcap"], a["log"], a["walks"], a["valid"], a["status"], None)
 
     def boxes(**kw):  # n2v_partition_forward_boxes: ragged mailboxes, the path records always to the log
-        a = dict(k=1, starts=p_, log=p_, n_parts=2)
+        a = dict(k=1, starts=p_, log=p_, n_parts=2, wide=0)
         a.update(kw)
-        return L.n2v_partition_forward_boxes(p_, 5, p_, p_, a["k"], 10, p_, a["n_parts"], 2, p_, p_, p_, 0, p_, p_,
+        return L.n2v_partition_forward_boxes(p_, 5, p_, p_, a["k"], 10, p_, a["n_parts"], 2, p_, p_, p_, a["wide"], p_, p_,
                                              p_, p_, a["starts"], a["log"], p_, None)
 
     assert boxes(k=0) == 0 and boxes(starts=0) == -1 and boxes(log=0) == -1 and boxes(n_parts=0) == -1
@@ -119,6 +119,11 @@ def test_partition_entry_points_validate_their_arguments():
     assert forward(carry=2, head_cols=4) == -1 and forward(k=-1) == -1 and forward(n_parts=0) == -1
     assert forward(log=0) == -1  # neither a log nor the output rows
     assert forward(carry=2, edge=0) == -1 and forward(carry=2, box_words=0) == -1 and forward(box_count=0) == -1
+    # wide is the width of a UNIFORM table: 0 or 1; a mixed table's n2v_graph.wedge_wide (T >= 2) is refused
+    for bad in (2, 24, 65536, -1):
+        assert forward(wide=bad) == -1 and forward(wide=bad, carry=0) == -1 and forward(wide=bad, carry=3) == -1
+    assert forward(wide=1, k=0) == 0 and forward(wide=2, k=0) == -1  # (refused before the empty batch returns)
+    assert boxes(k=0, wide=1) == 0 and boxes(wide=2) == -1 and boxes(wide=65536) == -1 and boxes(wide=-1) == -1
     assert L.n2v_partition_route(p_, 5, p_, 0, 0, 10, p_, 2, 0, p_, 0, 0, p_, p_, p_, p_, p_, None) == 0
     assert L.n2v_partition_route(p_, 3, p_, 0, 1, 10, p_, 2, 0, p_, 0, 0, p_, p_, p_, p_, p_, None) == -1
     assert L.n2v_partition_route(p_, 5, p_, 0, 1, 10, p_, 0, 0, p_, 0, 0, p_, p_, p_, p_, p_, None) == -1
@@ -130,6 +135,10 @@ def test_partition_entry_points_validate_their_arguments():
     assert L.n2v_gather_wedges(p_, p_, p_, 0, p_, p_, 0, p_, p_, 5, None) == 0
     assert L.n2v_gather_wedges(p_, p_, p_, 0, p_, p_, 1, p_, p_, 4, None) == -1
     assert L.n2v_gather_wedges(0, p_, p_, 0, p_, p_, 1, p_, p_, 5, None) == -1
+    for bad in (2, 65536, -1):
+        assert L.n2v_gather_wedges(p_, p_, p_, bad, p_, p_, 1, p_, p_, 5, None) == -1
+        assert L.n2v_gather_wedges(p_, p_, p_, bad, p_, p_, 0, p_, p_, 5, None) == -1
+    assert L.n2v_gather_wedges(p_, p_, p_, 1, p_, p_, 0, p_, p_, 5, None) == 0
 
 
 def test_product_package_never_touches_the_oracle():

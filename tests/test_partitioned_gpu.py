@@ -295,3 +295,92 @@ def test_partition_route_and_gathers_equal_plain_torch():
                                   for a, c in zip((o & ((1 << 40) - 1)).tolist(), ln[idx].tolist())])
                 assert torch.equal(out[:want.numel()], want)
 
+
+
+def _walk_all_routings(P, parts, start, num_walks, length, p, q, seed, want, wv):
+    """the default forwarding, the launch-per-stage routing and the ranks' form: all equal to n2v_walk"""
+    for forwarding in (None, False, "ranks"):
+        kw = {} if forwarding is None else {"forwarding": forwarding}
+        walks, valid = P.walk_partitioned_local(parts, start, num_walks, length, p, q, seed, **kw)
+        assert torch.equal(valid, wv), (p, q, forwarding)
+        assert torch.equal(walks, want), (p, q, forwarding)
+
+
+def test_parts_of_a_mixed_table_walk_on_32_bit_lists(oracle):
+    """a graph whose wedge table is MIXED (rows of 24 entries or more count as wide: build_wedges(wide_from=24)):
+    partition_graph rebuilds the table with 32-bit lists throughout, the forward kernel, n2v_gather_wedges and the
+    slices of wedge_pos run on uint32 -- same walks as n2v_walk on the whole graph, valid flags included, and as
+    the oracle on a sample"""
+    from node2vec_amd import partitioned as P
+    from node2vec_amd import randomwalk as rw
+    from node2vec_amd.graph import DeviceGraph
+
+    rng = np.random.default_rng(41)
+    nv = 1500
+    src = np.concatenate([rng.integers(0, nv, 12_000), rng.integers(0, 10, 1500)])
+    dst = np.concatenate([rng.integers(0, nv, 12_000), rng.integers(0, nv, 1500)])
+    a, b = np.concatenate([src, dst]), np.concatenate([dst, src])
+    out = a < nv - 25  # the last vertices have in-edges only: walkers vanish there
+    g = DeviceGraph.from_edges(a[out], b[out], None, n_vertices=nv, device="cuda")
+    g.build_wedges(wide_from=24)
+    g.wedge_tried = True
+    assert g.wedge_mode == 24 and int(g.degrees().max()) >= 24 and int(g.degrees().min()) < 24
+    parts = P.partition_graph(g, 4)
+    assert all(pt.wedge_pos is not None and pt.wedge_pos.dtype == torch.int32 for pt in parts)
+    assert sum(int((pt.edge_classes & 0xffffff).sum()) for pt in parts) == int((g.edge_classes & 0xffffff).sum()) > 0
+    start = rw.start_vertices(g)[::2].contiguous()
+    sample = start[::25].contiguous()
+    for p, q in ((0.5, 2.0), (4.0, 0.25), (3.0, 1.0), (1.0, 1.0)):
+        want, wv = rw.walk(g, start, 2, 12, p, q, 23)
+        assert not bool(wv.all())
+        _walk_all_routings(P, parts, start, 2, 12, p, q, 23, want, wv)
+        ow, ov = oracle.random_walk(g.rowptr.cpu().numpy(), g.col.cpu().numpy(), None, sample.cpu().numpy(), 2, 12,
+                                    p, q, 23)
+        walks, valid = P.walk_partitioned_local(parts, sample, 2, 12, p, q, 23)
+        gv = valid.cpu().numpy().astype(bool)
+        assert np.array_equal(gv, ov) and np.array_equal(walks.cpu().numpy()[gv], ow[ov])
+
+
+def test_a_row_of_more_than_65536_entries_walks_on_32_bit_positions(oracle):
+    """the smallest shape at which a truncation to 16 bits can show: a hub with 65 999 neighbours, a second vertex
+    u adjacent to the hub that shares 300 of them -- the 300 highest ids, at positions above 65 535 of the hub's
+    row -- 4 parts, walkers started on u, on the hub and on shared neighbours, 8 steps, q != 1.  The list of the
+    edge u -> hub, read from the part's tables before walking, holds positions >= 65 536.  Equal to n2v_walk; the
+    oracle rebuilds the hub's row of 65 999 entries at every step that stands on it, so its sample is 6 walkers."""
+    from node2vec_amd import partitioned as P
+    from node2vec_amd import randomwalk as rw
+    from node2vec_amd.graph import DeviceGraph
+
+    nv = 66_000
+    hub, u = 0, 1
+    others = np.arange(2, nv)
+    shared = np.arange(nv - 300, nv)
+    src = np.concatenate([np.full(others.size, hub), [hub], np.full(shared.size, u)])
+    dst = np.concatenate([others, [u], shared])
+    g = DeviceGraph.from_edges(np.concatenate([src, dst]), np.concatenate([dst, src]), None, n_vertices=nv,
+                               device="cuda")
+    assert int(g.degrees()[hub]) == nv - 1 >= 65_600
+    parts = P.partition_graph(g, 4)
+    assert g.wedge_mode == 65536  # the whole graph: a mixed table; the parts: 32-bit lists throughout
+    assert all(pt.wedge_pos is not None and pt.wedge_pos.dtype == torch.int32 for pt in parts)
+    # the list that leaves with a walker stepping u -> hub, from the tables of the part that owns u
+    pt = next(pt for pt in parts if pt.lo <= u < pt.hi)
+    row = pt.col[int(pt.rowptr[u - pt.lo]):int(pt.rowptr[u - pt.lo + 1])]
+    e = int(pt.rowptr[u - pt.lo]) + int(torch.nonzero(row == hub)[0])
+    n_list = int(pt.edge_classes[e] & 0xffffff)
+    at = int(pt.wedge_off[e] & P.WEDGE_OFF_MASK)
+    lst = pt.wedge_pos[at:at + n_list].cpu().numpy().view(np.uint32)
+    assert n_list == 300 and int(lst.min()) >= 65_536
+    hub_row = g.col[int(g.rowptr[hub]):int(g.rowptr[hub + 1])].cpu().numpy()
+    assert np.array_equal(hub_row[lst], shared)
+    # sorted, as the partitioned walk requires: the rows of a rank are a range of the start list
+    start = torch.tensor(sorted([u, hub, 2, 3, 40_000] + shared[::6].tolist()), dtype=torch.int32, device="cuda")
+    for p, q in ((0.5, 2.0), (4.0, 0.25)):
+        want, wv = rw.walk(g, start, 3, 8, p, q, 5)
+        assert bool(wv.all())
+        _walk_all_routings(P, parts, start, 3, 8, p, q, 5, want, wv)
+    few = torch.tensor(sorted([u, hub, nv - 1, nv - 300, 2, nv - 7]), dtype=torch.int32, device="cuda")
+    ow, ov = oracle.random_walk(g.rowptr.cpu().numpy(), g.col.cpu().numpy(), None, few.cpu().numpy(), 1, 8, 0.5, 2.0, 5)
+    walks, valid = P.walk_partitioned_local(parts, few, 1, 8, 0.5, 2.0, 5)
+    assert bool(ov.all()) and np.array_equal(valid.cpu().numpy().astype(bool), ov)
+    assert np.array_equal(walks.cpu().numpy(), ow)
