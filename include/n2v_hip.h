@@ -426,18 +426,10 @@ int n2v_walk_weighted_step(const n2v_graph *g, const int32_t *start_ids, int32_t
                            int64_t *scratch, const double *row_sums, const n2v_weighted_hubs *hubs,
                            void *stream);
 
-/* n2v_walk with a workspace lent by the caller (the library never allocates).  Exact biased walks
- * on a unit-weight graph that carries the hop and wedge tables, dyadic return_param / inout_param,
- * then run as passes over 32-byte walker records kept in the workspace: launches that hold the
- * quick exits and closed forms of the pairing loop (randomwalk.py:182-189) only, each followed by
- * a launch that replays the steps whose closed form declined -- same walks, bit for bit, as
- * n2v_walk (csrc/n2v_walk_wedge2.hip; measured SLOWER than the one-launch kernel on every BASELINE
- * graph).  That variant is a BUILD OPTION since round 5 (`make WEDGE2=1`): the default
- * library reports 0 bytes from n2v_walk_workspace_bytes and n2v_walk_ws is n2v_walk whatever it is lent.
- * (With the option: 4 main/replay rounds before the finishing launch, N2V_WEDGE2_ROUNDS overrides.)  n2v_walk_workspace_bytes says how many bytes the
- * call can use (0: this graph / mode / (p, q) has no use for one); workspace == NULL, or fewer
- * bytes than that, is n2v_walk.  The workspace must be 16-byte aligned; its contents mean nothing
- * before or after the call, and it may be reused by the next call on the same stream. */
+/* n2v_walk with a workspace lent by the caller, kept for callers of earlier releases.  No walk kernel
+ * takes a workspace (passes over walker records kept in one were measured SLOWER than the one-launch
+ * kernel on every BASELINE graph, DESIGN.md 5, and are gone): n2v_walk_workspace_bytes always returns 0,
+ * and n2v_walk_ws is n2v_walk whatever it is lent (workspace may be NULL). */
 int64_t n2v_walk_workspace_bytes(const n2v_graph *g, int64_t n_start, int32_t num_walks,
                                  int32_t walk_length, double return_param, double inout_param,
                                  int32_t mode);

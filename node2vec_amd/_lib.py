@@ -1,8 +1,8 @@
 """ctypes binding of node2vec_amd/libn2v_hip.so (the C ABI of include/n2v_hip.h).
 
 There is deliberately no fallback: a missing library or a missing GPU raises.
-N2V_HIP_LIB (environment) names another build of the SAME library (a -DN2V_CHECK / -DN2V_STATS
-diagnostic build, a timing variant of scripts/build_variants.sh): it must export every symbol of
+N2V_HIP_LIB (environment) names another build of the SAME library (an experiment's build kept
+beside the product): it must export every symbol of
 include/n2v_hip.h and the same ABI version, or the import fails.
 """
 import ctypes as C

@@ -9,23 +9,6 @@ namespace n2v {
 constexpr int kWavesPerBlock = 4;
 constexpr int kLdsChunks = 128;  // class ballots kept in LDS for rows <= 8192
 
-// diagnostic build only (-DN2V_STATS): per-wave counters / cycle stamps, flushed once
-#ifdef N2V_STATS
-static __device__ unsigned long long n2v_stats[40];  // one copy per translation unit
-struct WaveStats { unsigned long long v[40]; };
-#define N2V_STATS_ARG , WaveStats &WS
-#define N2V_STATS_PASS , WS
-#define N2V_STAT(i, v_) do { WS.v[i] += (unsigned long long)(v_); } while (0)
-#define N2V_T0 unsigned long long n2v_tprev = __builtin_readcyclecounter();
-#define N2V_T(i) do { unsigned long long tn_ = __builtin_readcyclecounter(); WS.v[i] += tn_ - n2v_tprev; n2v_tprev = tn_; } while (0)
-#else
-#define N2V_T0
-#define N2V_T(i) do { } while (0)
-#define N2V_STATS_ARG
-#define N2V_STATS_PASS
-#define N2V_STAT(i, v) do { } while (0)
-#endif
-
 constexpr int kBitWordsMax = 256;  // membership filter: up to 8192 bits
 constexpr int kMaybeCap = 128;     // filter hits waiting for exact verification
 
@@ -240,11 +223,7 @@ __device__ __forceinline__ double chunk_bias(const StepCtx &c, int chunk, int la
     int32_t x = valid ? c.vcol[i] : -1;
     is_ret = valid && x == c.s;
     is_mem = false;
-#if defined(N2V_ABLATE) && (N2V_ABLATE & 2)  // timing-only build: no membership search
-    if (c.need_mem) is_mem = false;
-#else
     if (c.need_mem) is_mem = member_sorted(c.scol, c.m, x, c.iters) && valid && !is_ret;
-#endif
     }
     if (!kFromCache && chunk < kLdsChunks) {
       uint64_t rm = ballot64(is_ret), mm = ballot64(is_mem);

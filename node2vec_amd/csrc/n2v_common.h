@@ -157,17 +157,11 @@ __device__ __forceinline__ int wedge_at_t(const void *base, int64_t k) {
 // there make 2 - 4 such searches, 10 - 25 k cycles in all (profiles/r7f_big_stats.log).  So a long range is
 // cut by SEVEN evenly spaced probes at a time -- independent loads, one round trip -- to an eighth, and
 // only the last 64 entries (two or three sectors) are searched by halving.
-#ifndef N2V_LIST_KARY
-#define N2V_LIST_KARY 1
-#endif
-#ifndef N2V_LIST_KARY_MIN
-#define N2V_LIST_KARY_MIN 64  // ranges above this many entries are cut 8-ary; below, by halving
-#endif
+constexpr int kListKaryMin = 64;  // ranges above this many entries are cut 8-ary; below, by halving
 template <typename P>
 __device__ __forceinline__ int list_lower_bound(const P *a, int cnt, int pos) {
   int lo = 0, hi = cnt;
-#if N2V_LIST_KARY
-  while (hi - lo > N2V_LIST_KARY_MIN) {
+  while (hi - lo > kListKaryMin) {
     const int step = (hi - lo) >> 3;
     int v[7];
 #pragma unroll
@@ -181,7 +175,6 @@ __device__ __forceinline__ int list_lower_bound(const P *a, int cnt, int pos) {
     lo = nlo;
     hi = nhi;
   }
-#endif
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
     if ((int)a[mid] < pos)

@@ -43,7 +43,7 @@ struct Row {
 };
 
 // Agent-scope accesses for rows of up to 128 floats (the XCDs' L2s are not coherent; the same
-// rule and measurements as N2V_SGNS_COHERENT in n2v_sgns.hip).  Wider rows stay plain.
+// rule and measurements as row_ld1 in n2v_sgns_rows.h).  Wider rows stay plain.
 __device__ __forceinline__ float ld1(const float *p) {
   return __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned int *>(p), __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_AGENT));

@@ -527,9 +527,6 @@ static int sgns_train_impl(const int32_t *walks, int64_t n_walks, int32_t walk_l
   if (P->max_waves > 0 && waves > P->max_waves) waves = P->max_waves;
   int64_t blocks = (waves + kSgnsWaves - 1) / kSgnsWaves;
   if (P->cum_index && (P->cum_index_bits < 1 || P->cum_index_bits > 30)) return N2V_EINVAL;
-#ifdef N2V_SGNS_TUNE
-  if (const char *e = getenv("N2V_SGNS_BLOCKS_PER_CU")) { int64_t cap = 256 * (int64_t)atoi(e); if (blocks > cap) blocks = cap; }
-#endif
   dim3 block(kSgnsWaves * 64);
   if (waves < kSgnsWaves) block = dim3((unsigned)waves * 64);
   if (P->deterministic) {
@@ -542,9 +539,7 @@ static int sgns_train_impl(const int32_t *walks, int64_t n_walks, int32_t walk_l
     return N2V_ELAUNCH;
   // lookahead depth: 1 pair for dim <= 512, none above (registers).  Depth 2 was measured
   // in rounds 2 and 3 (ring variant) and lost every time.
-#ifndef N2V_SGNS_DEPTH
 #define N2V_SGNS_DEPTH(VV) ((VV) <= 8 ? 1 : 0)
-#endif
 #define N2V_LAUNCH_R(VV, RR)                                                                  \
   do {                                                                                       \
     constexpr int kD = N2V_SGNS_DEPTH(VV);                   \

@@ -24,8 +24,8 @@ struct Row {
   float v[VEC];
 };
 
-// Rows are read and written with AGENT-SCOPE (`sc1`) accesses (N2V_SGNS_COHERENT, default 1; 0 = plain accesses, the
-// form of rounds 1 - 5).  The XCDs' L2s are not coherent with each other and a CU's L1 is never refreshed by another
+// Rows are read and written with AGENT-SCOPE (`sc1`) accesses (rounds 1 - 5 used plain
+// accesses).  The XCDs' L2s are not coherent with each other and a CU's L1 is never refreshed by another
 // CU's stores: with plain accesses a row trained by waves on two XCDs keeps the updates of ONE of them for as long
 // as a line stays cached -- a window of micro- to milliseconds where gensim's threads on a coherent CPU race over
 // nanoseconds.  Measured (round 6, profiles/r10m_sgns_coherent.log): of the rows a block of 768 sentences trains on a
@@ -36,24 +36,12 @@ struct Row {
 // dims of BASELINE cfgs 2 - 4): the 16-byte form (buffer loads / stores with aux = sc1 through a descriptor per row)
 // was built and measured too and costs 3.4 % at dim 256 and 31 % at dim 512 (profiles/r10n_sgns_coherent_rates.log),
 // so wider rows keep plain accesses.
-#ifndef N2V_SGNS_COHERENT
-#define N2V_SGNS_COHERENT 1
-#endif
-
 __device__ __forceinline__ float row_ld1(const float *p) {
-#if N2V_SGNS_COHERENT
   return __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned int *>(p), __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_AGENT));
-#else
-  return *p;
-#endif
 }
 __device__ __forceinline__ void row_st1(float *p, float x) {
-#if N2V_SGNS_COHERENT
   __hip_atomic_store(reinterpret_cast<unsigned int *>(p), __float_as_uint(x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-  *p = x;
-#endif
 }
 
 template <int VEC>
@@ -63,18 +51,12 @@ __device__ __forceinline__ void load_row(const float *base, int dim, int lane, b
     if constexpr (VEC == 1) {
       r.v[0] = row_ld1(base + lane);
     } else if constexpr (VEC == 2) {
-#if N2V_SGNS_COHERENT
       const unsigned long long u = __hip_atomic_load(reinterpret_cast<const unsigned long long *>(base + lane * 2),
                                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       r.v[0] = __uint_as_float((unsigned int)u);
       r.v[1] = __uint_as_float((unsigned int)(u >> 32));
-#else
-      float2 t = *reinterpret_cast<const float2 *>(base + lane * 2);
-      r.v[0] = t.x;
-      r.v[1] = t.y;
-#endif
     } else {
-      // (16-byte accesses stay plain: see N2V_SGNS_COHERENT)
+      // (16-byte accesses stay plain: see above row_ld1)
 #pragma unroll
       for (int q = 0; q < VEC / 4; ++q) {
         float4 t = *reinterpret_cast<const float4 *>(base + lane * VEC + q * 4);
@@ -100,14 +82,10 @@ __device__ __forceinline__ void store_row(float *base, int dim, int lane, bool f
     if constexpr (VEC == 1) {
       row_st1(base + lane, r.v[0]);
     } else if constexpr (VEC == 2) {
-#if N2V_SGNS_COHERENT
       const unsigned long long u = (unsigned long long)__float_as_uint(r.v[0]) |
                                    ((unsigned long long)__float_as_uint(r.v[1]) << 32);
       __hip_atomic_store(reinterpret_cast<unsigned long long *>(base + lane * 2), u, __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);
-#else
-      *reinterpret_cast<float2 *>(base + lane * 2) = make_float2(r.v[0], r.v[1]);
-#endif
     } else {
 #pragma unroll
       for (int q = 0; q < VEC / 4; ++q)

@@ -13,42 +13,16 @@
 
 namespace n2v {
 
-// diagnostic build only (-DN2V_CHECK): out-of-range values are recorded in status[0] (bits 8..)
-// and clamped instead of being used as addresses
-#ifdef N2V_CHECK
-static __device__ uint32_t *n2v_check_status;
-#define N2V_CHECK_RANGE(code, val, lo_, hi_)                                  \
-  do {                                                                         \
-    if ((val) < (lo_) || (val) >= (hi_)) {                                     \
-      atomicOr(n2v_check_status, 1u << (8 + (code)));                          \
-      (val) = (lo_);                                                           \
-    }                                                                          \
-  } while (0)
-#else
-#define N2V_CHECK_RANGE(code, val, lo_, hi_) do { } while (0)
-#endif
-
 template <typename T>
 __device__ __forceinline__ T pick3(bool first, bool second, T a, T b, T c) {
   return first ? a : (second ? b : c);
 }
 
-// diagnostic build (-DN2V_DECLINE_STATS): why lane_case_a_jump (codes 1 ..) / lane_case_b_jump (11 ..) return -1 on rows of
-// more than 64 slots (words 8 + code of the launch's status) and of 4096 and more (words 40 + code); scripts/r6/decline_stats.py
-// lends the launch 128 words.  Round 6, cfg 4 trimmed at 100 000 (profiles/r11d_decline_stats.log): every decline on such a
-// row is a TIE of the exact process (codes 3, 5, 15, 20) -- the reference's rounding decides it and only a replay knows.
-#ifdef N2V_DECLINE_STATS
-static __device__ uint32_t *n2v_decline_words;
-#define N2V_DECLINE(code)                                            \
-  do {                                                               \
-    atomicAdd(n2v_decline_words + 256 + (code), 1u); /* rows of any length */                       \
-    if (n > 64) atomicAdd(n2v_decline_words + ((code) < 32 ? (code) : 96 + (code)), 1u);           \
-    if (n >= 4096 && (code) < 32) atomicAdd(n2v_decline_words + 32 + (code), 1u);   \
-    return -1;                                                       \
-  } while (0)
-#else
+// why lane_case_a_jump (codes 1 ..) / lane_case_b_jump (11 ..) return -1.  A diagnostic build counted the codes on rows
+// of more than 64 slots and of 4096 and more.  Round 6, cfg 4 trimmed at 100 000 (profiles/r11d_decline_stats.log): every
+// decline on such a row is a TIE of the exact process (codes 3, 5, 15, 20) -- the reference's rounding decides it and only a
+// replay knows.
 #define N2V_DECLINE(code) return -1
-#endif
 
 struct UnitConsts {
   double bR, bM, bO;     // 1/p, 1, 1/q
@@ -333,7 +307,7 @@ template <typename P>
 __device__ __forceinline__ int unlisted_from_top(int n, int nM, const ListRef<P> &list, int T) {
   const int c = n - T - nM;
   int lo = 0, hi = nM;  // the number of k with list[k] - k <= c
-  while (hi - lo > N2V_LIST_KARY_MIN) {  // seven independent probes per round trip (as list_lower_bound)
+  while (hi - lo > kListKaryMin) {  // seven independent probes per round trip (as list_lower_bound)
     const int step = (hi - lo) >> 3;
     int v[7];
 #pragma unroll
@@ -661,9 +635,6 @@ __device__ __forceinline__ int lane_case_b(int n, int pick, double r2, double vR
                                            double vO, int nR, int rpos, int nM, ListRef<P> list,
                                            bool pickR, bool pickM, int lo_pick = -1, int below = -1) {
   const int nO = n - nR - nM;
-#if defined(N2V_ABLATE_B) && N2V_ABLATE_B == 1  // timing only: the replay does nothing
-  return pick;
-#endif
   auto list_lower = [&](int pos) -> int {  // entries of the list below pos
     return list_lower_bound<P>(list, nM, pos);
   };
@@ -673,9 +644,6 @@ __device__ __forceinline__ int lane_case_b(int n, int pick, double r2, double vR
     return (nM - list_lower(pos)) + r;
   };
   auto other_pos = [&](int t) -> int {  // position of the t-th "other" slot from the top; 0 if none
-#if defined(N2V_ABLATE_B) && N2V_ABLATE_B == 2  // timing only: no search for the slot of a rank
-    return pick;
-#endif
     if (t < 1 || t > nO) return 0;
     return other_from_top<P>(n, nR, rpos, nM, list, t);
   };
@@ -707,9 +675,6 @@ __device__ __forceinline__ int lane_case_b(int n, int pick, double r2, double vR
     if (i_next > S) break;  // underfull is empty (:182)
     if (!have_cur && t_used >= nO) break;  // overfull is empty (:182)
     const int i_cur = i_next++;
-#ifdef N2V_DECLINE_STATS
-    atomicAdd(n2v_decline_words + 81, 1u);  // iterations of this loop
-#endif
     const double uv = (i_cur > mA && i_cur <= mA + nR) ? vR : vM;
     const int over_rank = t_used + 1;
     if (i_cur == i_pick) return other_pos(over_rank);  // alias[pick]; r2 >= probs[pick] here
@@ -742,15 +707,6 @@ __device__ __forceinline__ int lane_case_b(int n, int pick, double r2, double vR
     }
     // j = the first i >= 1 with a1 + i d >= 1: slots 1 .. j are demoted, slot j + 1 settles
     double j = fmin(fmax(ceil(need * inv), 1.0), m1);
-#ifdef N2V_DECLINE_STATS
-    {
-      double jj = j;
-      unsigned fix = 0;
-      while (jj * d < need) { jj += 1.0; ++fix; }
-      while (jj >= 2.0 && (jj - 1.0) * d >= need) { jj -= 1.0; ++fix; }
-      atomicAdd(n2v_decline_words + 82, fix);  // corrections of the cascade length
-    }
-#endif
     while (j * d < need) j += 1.0;
     while (j >= 2.0 && (j - 1.0) * d >= need) j -= 1.0;
     const int jd = (int)j;
@@ -1313,15 +1269,6 @@ int n2v_walk_wedge_try(const n2v_graph *g, const int32_t *start_ids, int64_t n_s
                        int32_t num_walks, int32_t walk_length, double p, double q,
                        const n2v::UnitConsts &K, uint64_t seed, int32_t *walks_out,
                        uint8_t *valid_out, uint32_t *status, void *stream);
-
-// the same walk in passes over a caller-lent workspace (n2v_walk_wedge2.hip): closed forms in the
-// main launches, declined steps replayed out of line.  1 = enqueued, 0 = does not apply
-int64_t n2v_walk_wedge2_workspace(int64_t total);
-int n2v_walk_wedge2_try(const n2v_graph *g, const int32_t *start_ids, int64_t n_start,
-                        int32_t num_walks, int32_t walk_length, double p, double q,
-                        const n2v::UnitConsts &K, uint64_t seed, int32_t *walks_out,
-                        uint8_t *valid_out, uint32_t *status, void *workspace,
-                        int64_t workspace_bytes, int32_t rounds, void *stream);
 
 // the wedge-list instance of n2v_partition_step (n2v_walk_wedge.hip): 1 = launched, < 0 on error
 int n2v_partition_step_wedge_launch(const int64_t *rowptr, const int32_t *col, int64_t lo,

@@ -138,7 +138,7 @@ __device__ __forceinline__ double load_vals(const StepCtx &c, WaveLds &L, int ch
 // come 64 at a time from ballots over a chunk of probs0 = b / avg.
 template <bool kCached>
 __device__ __forceinline__ int pairing(const StepCtx &c, WaveLds &L, int lane, int pick,
-                                       double avg, double p_pick, double r2, bool bq_valid N2V_STATS_ARG) {
+                                       double avg, double p_pick, double r2, bool bq_valid) {
   const int n = c.n;
   // Rows longer than the LDS cache re-read their weights from HBM/L2.  The loop
   // below is serial, so that latency would be fully exposed at every refill: each
@@ -184,7 +184,6 @@ __device__ __forceinline__ int pairing(const StepCtx &c, WaveLds &L, int lane, i
   double fin_prob = p_pick;
   int fin_alias = 0;
   for (;;) {
-    N2V_STAT(9, 1);
     while (om == 0ull && co > 0) {  // next overfull candidates
       --co;
       bool valid;
@@ -236,7 +235,6 @@ __device__ __forceinline__ int pairing(const StepCtx &c, WaveLds &L, int lane, i
       um &= ~run;
       bool demoted = false;
       while (run != 0ull) {
-        N2V_STAT(8, 1);
         const int l = 63 - __clzll((long long)run);
         run ^= 1ull << l;
         r = r + readlane_f64(uval, l) - 1.0;  // probs[over] = probs[over] + probs[under] - 1.0
@@ -268,22 +266,17 @@ __device__ __forceinline__ int pairing(const StepCtx &c, WaveLds &L, int lane, i
 // Index drawn by sampling_from_alias(r1, r2) on the table that
 // generate_edge_alias_tables would build.  Returns -1 on ZeroDivisionError.
 __device__ __forceinline__ int exact_draw(const StepCtx &c, uint32_t u1, uint32_t u2,
-                                          int lane, WaveLds &L N2V_STATS_ARG) {
+                                          int lane, WaveLds &L) {
   const int n = c.n;
   const int pick = pick_index(u1, n);  // int(r1 * n), r1 = u1 / 2^32
   const double r2 = (double)u2 * (1.0 / 4294967296.0);
 
-  N2V_T0
   // ---- pass 0: hashed-id filter of N(s) in LDS ---------------------------------
   // Membership "x in N(s)" (:226) costs a dependent chain of ~log2(m) gathers per
   // 64 neighbours when searched directly.  Instead every y of N(s) sets one bit;
   // pass 1 tests one bit per x; only the hits (true members + a few false
   // positives) are verified by binary search, batched once per step.
-#if defined(N2V_ABLATE) && (N2V_ABLATE & 8)  // timing-only: no filter, no search at all
-  const bool use_filter = false;
-#else
   const bool use_filter = c.lst == nullptr && c.need_mem && c.m <= 4096 && c.m <= 8 * n + 64;
-#endif
   int shift = 32;
   if (use_filter) {
     int words = 64;
@@ -311,8 +304,6 @@ __device__ __forceinline__ int exact_draw(const StepCtx &c, uint32_t u1, uint32_
     __builtin_amdgcn_wave_barrier();
   }
 
-  N2V_T(16);
-  N2V_STAT(0, 1); N2V_STAT(1, use_filter ? 1 : 0); N2V_STAT(2, (c.need_mem && !use_filter) ? 1 : 0);
   // ---- pass 1: stream N(v): classify, bias, sum ----------------------------------
   SumState st;
   st.isum = 0;
@@ -350,9 +341,7 @@ __device__ __forceinline__ int exact_draw(const StepCtx &c, uint32_t u1, uint32_
         if (chunk0 + u < c.nch) tmask[u] = lst_chunk_mask(c, chunk0 + u, lane, lm_fwd, L.flags);
     }
     if (c.need_mem && !use_filter && !tables) {
-#if !(defined(N2V_ABLATE) && (N2V_ABLATE & 2))
       member_sorted_x4(c.scol, c.m, xs, c.iters, memv);  // 4 interleaved searches
-#endif
     }
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
@@ -416,12 +405,7 @@ __device__ __forceinline__ int exact_draw(const StepCtx &c, uint32_t u1, uint32_
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  N2V_T(17);
-#if !(defined(N2V_ABLATE) && (N2V_ABLATE & 4))  // timing-only: no verification of filter hits
   if (mcount) verify_maybes(c, L, mcount, lane, pick, st);
-#endif
-  N2V_STAT(3, mcount); N2V_STAT(4, (mcount + 63) / 64);
-  N2V_T(18);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
 
@@ -452,47 +436,26 @@ __device__ __forceinline__ int exact_draw(const StepCtx &c, uint32_t u1, uint32_
   if (avg == 0.0) return -1;
   const double p_pick = readfirstlane_f64(b_pick / avg);    // :173
 
-  N2V_T(19);
   // untouched underfull slot: probs[pick] never changes, alias irrelevant
   if (p_pick < 1.0 && r2 < p_pick) return pick;
-  N2V_STAT(5, 1);
-#if defined(N2V_ABLATE) && (N2V_ABLATE & 1)  // timing-only build: no pairing pass
-  return pick;
-#endif
   // x -> x / avg is monotone, so the extreme weights decide whether either stack
   // is empty; then the pairing loop (:182) never runs: alias stays 0, probs stay.
-#if defined(N2V_ABLATE) && (N2V_ABLATE & 64)  // timing-only: stop before the min/max shortcut
-  return pick;
-#endif
   double bmin = st.bmin, bmax = st.bmax;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     bmin = fmin(bmin, __shfl_xor(bmin, off, 64));
     bmax = fmax(bmax, __shfl_xor(bmax, off, 64));
   }
-  N2V_T(20);
   bmin = readfirstlane_f64(bmin);
   bmax = readfirstlane_f64(bmax);
   if (!(bmin / avg < 1.0) || (bmax / avg < 1.0)) return (r2 < p_pick) ? pick : 0;
 
-  N2V_STAT(6, 1); N2V_STAT(7, n <= 64 ? 1 : 0); N2V_STAT(10, (bq_valid && n <= kBqCap) ? 0 : 1);
   // ---- pass 2: LIFO pairing (:182-189) until slot `pick` is final ------------
-#if defined(N2V_ABLATE) && (N2V_ABLATE & 16)  // timing-only: run the pairing twice
   if (bq_valid && n <= kBqCap) {
-    int tmp = pairing<true>(c, L, lane, pick, avg, p_pick, r2, bq_valid N2V_STATS_PASS);
-    asm volatile("" ::"v"(tmp));
-  }
-#endif
-  if (bq_valid && n <= kBqCap) {
-    const int res = pairing<true>(c, L, lane, pick, avg, p_pick, r2, bq_valid N2V_STATS_PASS);
-    N2V_T(21);
+    const int res = pairing<true>(c, L, lane, pick, avg, p_pick, r2, bq_valid);
     return res;
   }
-#if defined(N2V_ABLATE) && (N2V_ABLATE & 32)  // timing-only: no pairing on uncached rows
-  return pick;
-#endif
-  const int res2 = pairing<false>(c, L, lane, pick, avg, p_pick, r2, bq_valid N2V_STATS_PASS);
-  N2V_T(22);
+  const int res2 = pairing<false>(c, L, lane, pick, avg, p_pick, r2, bq_valid);
   return res2;
 }
 
@@ -531,11 +494,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 7) void walk_exact_kernel(
   StepCtx c;
   c.p = p;
   c.q = q;
-#ifdef N2V_STATS
-  WaveStats WS;
-  for (int i = 0; i < 40; ++i) WS.v[i] = 0;
-  const unsigned long long t_kernel0 = __builtin_readcyclecounter();
-#endif
 
   // walkers are taken from a shared counter (status[1], zero at launch), not by a fixed
   // stride: their costs differ widely and no wave should sit on a long queue while others idle
@@ -620,7 +578,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 7) void walk_exact_kernel(
         }
         step_tables(c, g, e_prev);
         const uint64_t bits = step_bits(h0, (uint32_t)step);
-        const int idx = exact_draw(c, (uint32_t)(bits >> 32), (uint32_t)bits, lane, L N2V_STATS_PASS);
+        const int idx = exact_draw(c, (uint32_t)(bits >> 32), (uint32_t)bits, lane, L);
         if (idx < 0) {
           if (lane == 0) atomicOr(status, N2V_ST_ZERODIV);
           alive = false;
@@ -649,11 +607,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 7) void walk_exact_kernel(
     }
     if (lane == 0) valid_out[r] = alive ? 1 : 0;
   }
-#ifdef N2V_STATS
-  WS.v[23] = __builtin_readcyclecounter() - t_kernel0;
-  if (lane == 0)
-    for (int i = 0; i < 40; ++i) atomicAdd(&n2v_stats[i], WS.v[i]);
-#endif
 }
 
 
@@ -677,10 +630,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 7) void partition_step_kernel(
   const int lane = threadIdx.x & 63;
   WaveLds &L = lds_all[threadIdx.x >> 6];
   if (lane < 16) reinterpret_cast<uint32_t *>(L.flags)[lane] = 0u;
-#ifdef N2V_STATS
-  WaveStats WS;
-  for (int i = 0; i < 40; ++i) WS.v[i] = 0;
-#endif
   StepCtx c;
   c.p = p;
   c.q = q;
@@ -728,7 +677,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 7) void partition_step_kernel(
       }
       if (ok) {
         const uint64_t bits = step_bits(walker_stream(seed, key), step);
-        const int idx = exact_draw(c, (uint32_t)(bits >> 32), (uint32_t)bits, lane, L N2V_STATS_PASS);
+        const int idx = exact_draw(c, (uint32_t)(bits >> 32), (uint32_t)bits, lane, L);
         if (idx < 0) {
           if (lane == 0) atomicOr(status, N2V_ST_ZERODIV);
         } else {
@@ -760,10 +709,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 7) void weighted_step_wave_ker
   const int lane = threadIdx.x & 63;
   WaveLds &L = lds_all[threadIdx.x >> 6];
   if (lane < 16) reinterpret_cast<uint32_t *>(L.flags)[lane] = 0u;
-#ifdef N2V_STATS
-  WaveStats WS;
-  for (int i = 0; i < 40; ++i) WS.v[i] = 0;
-#endif
   const int L1 = walk_length + 1;
   StepCtx c;
   c.p = p;
@@ -814,7 +759,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 7) void weighted_step_wave_ker
     step_tables(c, g, first ? -1 : readfirstlane_i64(edge_state[r]));
     const uint64_t key = (uint64_t)start_ids[r / num_walks] * (uint64_t)num_walks + (uint64_t)(r % num_walks);
     const uint64_t bits = step_bits(walker_stream(seed, key), (uint32_t)step);
-    const int idx = exact_draw(c, (uint32_t)(bits >> 32), (uint32_t)bits, lane, L N2V_STATS_PASS);
+    const int idx = exact_draw(c, (uint32_t)(bits >> 32), (uint32_t)bits, lane, L);
     if (lane == 0) {
       if (idx < 0) {  // ZeroDivisionError (:172-173)
         atomicOr(status, N2V_ST_ZERODIV);
@@ -875,16 +820,6 @@ extern "C" int n2v_partition_step_generic_launch(const int64_t *rowptr, const in
   return N2V_OK;
 }
 
-#ifdef N2V_STATS
-extern "C" int n2v_debug_stats(unsigned long long *out_host, int reset) {
-  if (hipMemcpyFromSymbol(out_host, HIP_SYMBOL(n2v::n2v_stats), sizeof(unsigned long long) * 40) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[40] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(n2v::n2v_stats), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif
 
 // the long rows of n2v_walk_weighted_step (n2v_walk_wlanes.hip): status[1] must be zero at launch
 extern "C" int n2v_weighted_step_wave_launch(const n2v_graph *g, const int32_t *start_ids, int32_t num_walks,

@@ -265,13 +265,11 @@ __device__ __forceinline__ void verify_unit(const UnitStep &c, UnitLds &L, int c
 
 template <bool kDyadic>
 __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K, uint32_t u1,
-                                         uint32_t u2, int lane, UnitLds &L N2V_STATS_ARG) {
+                                         uint32_t u2, int lane, UnitLds &L) {
   const int n = c.n;
   const int pick = pick_index(u1, n);  // int(r1 * n)
   const double r2 = (double)u2 * (1.0 / 4294967296.0);
 
-  N2V_T0
-  N2V_STAT(0, 1);
   int nR = 0, nM = 0;
   int sp_n = -1;  // >= 0: L.pool holds the position of every return/shared slot below the cached chunks
   // ---- reverse classification: search from the SHORTER list --------------------------
@@ -307,7 +305,6 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
         else
           j = wedge_at_t<uint16_t>(c.w_pos, k - nR);
       }
-      N2V_CHECK_RANGE(5, j, 0, n);
       const int ci = c.nch - 1 - (j >> 6);
       if (act && ci < kUC)
         atomicOr(reinterpret_cast<unsigned long long *>(&L.cls[2 * ci + (isr ? 0 : 1)]),
@@ -323,8 +320,6 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
     if (sp_n > kSparseCap) sp_n = -1;  // too many: the uncached chunks are searched on demand
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    N2V_T(24);
-    N2V_STAT(13, 1);
   } else if (reverse) {
     const int ncached = c.nch < kUC ? c.nch : kUC;
     for (int wv = lane; wv < 2 * ncached; wv += 64) L.cls[wv] = 0ull;
@@ -389,8 +384,6 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
     if (sp_n > kSparseCap) sp_n = -1;  // too many: the uncached chunks are searched again on demand
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    N2V_T(24);
-    N2V_STAT(13, 1);
   } else {
   // ---- pass 0: membership strategy for "x in N(s)" (:226) ---------------------------
   //  staged  m <= 1024: N(s) is copied into LDS; rows of v up to 2 chunks search it
@@ -447,9 +440,6 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
     __builtin_amdgcn_wave_barrier();
   }
 
-  N2V_T(16);
-  N2V_STAT(1, (staged && use_filter) ? 1 : 0); N2V_STAT(2, (c.need_mem && !staged && !big_filter) ? 1 : 0);
-  N2V_STAT(11, (staged && !use_filter) ? 1 : 0); N2V_STAT(12, big_filter ? 1 : 0);
   // ---- pass 1: stream N(v) ids, classify, count ---------------------------------
   int mcount = 0;
   // classify one chunk given its ids and (outside filter mode) the membership flags
@@ -565,16 +555,11 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
-#ifdef N2V_STATS
-  if (merge) { N2V_T(22); N2V_STAT(5, 1); } else if (direct) { N2V_T(20); } else { N2V_T(17); }
-#endif
-  N2V_STAT(3, mcount);
   if (mcount) verify_unit(c, L, mcount, lane, staged, nM);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
 
   }
-  N2V_T(18);
   // ---- :172-173 on three values -----------------------------------------------------
   const int nO = n - nR - nM;
   double avg;
@@ -610,7 +595,6 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
   chunk_classes(c, L, pick >> 6, lane, sp_n, prm, pmm);
   const bool pR = (prm >> (pick & 63)) & 1ull, pM = (pmm >> (pick & 63)) & 1ull;
   const double p_pick = readfirstlane_f64(pick3(pR, pM, K.bR, K.bM, K.bO) / avg);
-  N2V_T(19);
   if (p_pick < 1.0 && r2 < p_pick) return pick;  // untouched underfull slot
   // uniform values: scalar registers, so they cost no VGPRs across the pairing code
   const double vR = pR ? p_pick : readfirstlane_f64(K.bR / avg);
@@ -621,7 +605,6 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
   const bool any_over = (nR && !uR) || (nM && !uM) || (nO && !uO);
   if (!any_under || !any_over) return (r2 < p_pick) ? pick : 0;  // the loop of :182 never runs
 
-  N2V_STAT(6, 1);
   // ---- pairing, count-based fast path ----------------------------------------------
   // When "other" is the ONLY underfull class every absorbed slot has the same value
   // vO, so the fp64 sequence of :186 depends on how MANY slots an overfull absorbs,
@@ -630,7 +613,6 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
   // class ballots.  The stack discipline is unchanged: overfull slots are taken in
   // descending index order, a demoted one is absorbed first by its successor.
   const int top_cached_chunk = c.nch - kUC;  // chunks below this are not in LDS
-#ifndef N2V_NO_CASE_A
   if (uO && !(nR && uR) && !(nM && uM) && (pick >> 6) >= top_cached_chunk) {
     const int total_u = nO;
     int above = total_u + 1;  // underfull slots consumed before `pick` is next (never, if overfull)
@@ -702,7 +684,6 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
         j = __builtin_amdgcn_readfirstlane(j);
       }
       while (j + 4 <= limit) {
-        N2V_STAT(8, 4);
         const double a1 = r + vO - 1.0;
         const double a2 = a1 + vO - 1.0;
         const double a3 = a2 + vO - 1.0;
@@ -729,7 +710,6 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
         break;
       }
       while (!demoted && j < limit) {
-        N2V_STAT(8, 1);
         r = r + vO - 1.0;
         ++j;
         if (r < 1.0) demoted = true;
@@ -750,10 +730,8 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
       }
       break;
     }
-    N2V_T(21);
     return (r2 < fprob) ? pick : falias;
   }
-#endif
   // ---- pairing, run engine (every other class arrangement) -----------------------------
   // Both Python stacks are consumed in descending index order and their interleaving does
   // not matter, only each stack's own order.  With three class values a stack is a
@@ -879,8 +857,6 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
         }
         looked = true;
         --S.c;
-        N2V_STAT(10, 1);
-        if (c.nch - 1 - S.c >= kUC) N2V_STAT(7, 1);
         chunk_classes(c, L, S.c, lane, sp_n, S.rm, S.mm);
         const uint64_t vm = valid_mask(c, S.c);
         const uint64_t um = (uR ? S.rm : 0ull) | (uM ? S.mm : 0ull) | (uO ? (vm & ~(S.rm | S.mm)) : 0ull);
@@ -1007,7 +983,6 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
             falias = kth_index(O.run, O.homog ? O.base : O.rc, O.used + 1);
             return;
           }
-          N2V_STAT(9, 1);
           const double val = O.val;
           const int avail = O.cnt - O.used;
           int k;
@@ -1066,7 +1041,6 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
             j = __builtin_amdgcn_readfirstlane(j);
           }
           while (j + 4 <= count) {
-            N2V_STAT(8, 4);
             const double a1 = r + val - 1.0;
             const double a2 = a1 + val - 1.0;
             const double a3 = a2 + val - 1.0;
@@ -1093,7 +1067,6 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
             break;
           }
           while (!demoted && j < count) {
-            N2V_STAT(8, 1);
             r = r + val - 1.0;
             ++j;
             if (r < 1.0) demoted = true;
@@ -1106,17 +1079,14 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
         u_is_pick = cur_is_pick;
       }
     }();
-    N2V_T(21);
     return (r2 < fprob) ? pick : falias;
   }
 }
 
 // 8 waves per SIMD (<= 64 VGPRs) matches the 8 resident blocks the 20 KB of LDS allow
-#ifndef N2V_UNIT_WAVES
-#define N2V_UNIT_WAVES 8
-#endif
+constexpr int kUnitWaves = 8;
 template <bool kDyadic>
-__global__ __launch_bounds__(kWavesPerBlock * 64, N2V_UNIT_WAVES) void walk_exact_unit_kernel(
+__global__ __launch_bounds__(kWavesPerBlock * 64, kUnitWaves) void walk_exact_unit_kernel(
     n2v_graph g, const int32_t *__restrict__ start_ids, int64_t n_start, int32_t num_walks,
     int32_t walk_length, double p, double q, UnitConsts K, uint64_t seed,
     int32_t *__restrict__ walks_out, uint8_t *__restrict__ valid_out,
@@ -1131,11 +1101,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_UNIT_WAVES) void walk_exac
   const bool biased = !(p == 1.0 && q == 1.0);
   UnitStep c;
   c.need_mem = q != 1.0;
-#ifdef N2V_STATS
-  WaveStats WS;
-  for (int i = 0; i < 40; ++i) WS.v[i] = 0;
-  const unsigned long long t_kernel0 = __builtin_readcyclecounter();
-#endif
 
   // Walkers differ a lot in cost (a walk that lingers among hubs is many times dearer than one
   // in the periphery), so waves take them from a shared counter (status[1], zero at launch)
@@ -1161,9 +1126,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_UNIT_WAVES) void walk_exac
     if (rr >= total) break;
     const int64_t r = readfirstlane_i64(rr);
     if (!dynamic) rr += n_waves;
-#ifdef N2V_STATS
-    const unsigned long long t_walker0 = __builtin_readcyclecounter();
-#endif
     int32_t *out = walks_out + r * L1;
     // the path lives in registers (lane t holds vertices t and 64 + t) and is stored as
     // whole rows at the end; walks longer than 128 vertices fall back to direct stores
@@ -1216,18 +1178,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_UNIT_WAVES) void walk_exac
           c.scol = g.col + sb;
           c.m = m;
           c.iters = 32 - __clz(m);
-#ifdef N2V_STATS
-          const unsigned long long t_s0 = __builtin_readcyclecounter();
-#endif
-          idx = unit_draw<kDyadic>(c, K, (uint32_t)(bits >> 32), (uint32_t)bits, lane, L N2V_STATS_PASS);
-#ifdef N2V_STATS
-          {
-            const unsigned long long dt = __builtin_readcyclecounter() - t_s0;
-            const int bk = n <= 64 ? 0 : (n <= 1024 ? 1 : (n <= 4096 ? 2 : (n <= 8192 ? 3 : 4)));
-            WS.v[25 + bk] += dt;
-            if (bk >= 3) WS.v[14 + bk - 3] += 1;  // 14: 4096 < n <= 8192, 15: larger
-          }
-#endif
+          idx = unit_draw<kDyadic>(c, K, (uint32_t)(bits >> 32), (uint32_t)bits, lane, L);
         }
         const int32_t next = __builtin_amdgcn_readfirstlane(g.col[vb + idx]);
         if (buffered) {
@@ -1252,19 +1203,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_UNIT_WAVES) void walk_exac
       if (64 + lane < L1) out[64 + lane] = path1;
     }
     if (lane == 0) valid_out[r] = alive ? 1 : 0;
-#ifdef N2V_STATS
-    {  // slowest walker and when the wave took it (tail diagnostics)
-      const unsigned long long tw = __builtin_readcyclecounter() - t_walker0;
-      if (lane == 0) atomicMax(&n2v_stats[30], tw);
-      WS.v[31] += tw;
-    }
-#endif
   }
-#ifdef N2V_STATS
-  WS.v[23] = __builtin_readcyclecounter() - t_kernel0;
-  if (lane == 0)
-    for (int i = 0; i < 40; ++i) atomicAdd(&n2v_stats[i], WS.v[i]);
-#endif
 }
 
 // ---- one step of the walkers resident on one part of a partitioned graph -------------------
@@ -1274,7 +1213,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_UNIT_WAVES) void walk_exac
 // (Rows travel here.  When wedge lists travel instead the step is per-lane work:
 // partition_step_wedge_kernel, n2v_walk_wedge.hip.)
 template <bool kDyadic>
-__global__ __launch_bounds__(kWavesPerBlock * 64, N2V_UNIT_WAVES) void partition_step_unit_kernel(
+__global__ __launch_bounds__(kWavesPerBlock * 64, kUnitWaves) void partition_step_unit_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, int64_t lo,
     int64_t n_local, const int64_t *__restrict__ head, int head_cols,
     const int64_t *__restrict__ src_ptr, const int32_t *__restrict__ src_ids,
@@ -1286,10 +1225,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_UNIT_WAVES) void partition
   const bool biased = !(p == 1.0 && q == 1.0);
   UnitStep c;
   c.need_mem = q != 1.0;
-#ifdef N2V_STATS
-  WaveStats WS;
-  for (int i = 0; i < 40; ++i) WS.v[i] = 0;
-#endif
   ItemQueue queue(k, kWavesPerBlock);
   for (;;) {
     const int64_t i = queue.next(&status[1], lane);
@@ -1333,7 +1268,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_UNIT_WAVES) void partition
             if (!ok && lane == 0) atomicOr(status, N2V_ST_RANGE);
           }
           if (ok)
-            idx = unit_draw<kDyadic>(c, K, (uint32_t)(bits >> 32), (uint32_t)bits, lane, L N2V_STATS_PASS);
+            idx = unit_draw<kDyadic>(c, K, (uint32_t)(bits >> 32), (uint32_t)bits, lane, L);
         }
         if (idx >= 0) {
           next = __builtin_amdgcn_readfirstlane(col[vb + idx]);
@@ -1363,14 +1298,12 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_UNIT_WAVES) void partition
 // the whole wave running unit_draw (the routine of the wave-per-walker kernel, unchanged: same
 // bits).  Dyadic p, q only (the row sum is then an integer combination of the counts); p == q
 // == 1 needs no counts at all (every step is `pick`).
-#ifndef N2V_LANES_WAVES
-#define N2V_LANES_WAVES 5
-#endif
+constexpr int kLanesWaves = 5;
 // kHops: the hop table (n2v_hops_build) is at hand -- the entry that names the next vertex also
 // carries its row pointer, its degree and the class counts of the edge just walked (needed at
 // the next step), so the quick phase of a step is ONE 16-byte gather plus the membership test.
 template <bool kHops>
-__global__ __launch_bounds__(kWavesPerBlock * 64, N2V_LANES_WAVES) void walk_exact_unit_lanes_kernel(
+__global__ __launch_bounds__(kWavesPerBlock * 64, kLanesWaves) void walk_exact_unit_lanes_kernel(
     n2v_graph g, const int32_t *__restrict__ start_ids, int64_t n_start, int32_t num_walks,
     int32_t walk_length, double p, double q, UnitConsts K, uint64_t seed,
     int32_t *__restrict__ walks_out, uint8_t *__restrict__ valid_out,
@@ -1384,19 +1317,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_LANES_WAVES) void walk_exa
   const bool need_mem = q != 1.0;
   // wedge table (n2v_wedge_build): the class of every slot of a step's table by position
   const bool have_w = g.wedge_off != nullptr && g.wedge_pos != nullptr;
-#ifdef N2V_CHECK
-  n2v_check_status = status;
-  const int dbg = g.reserved;  // bit 0: no per-lane pairing, 1: no list classification, 2: no list membership
-#else
-  constexpr int dbg = 0;
-#endif
   UnitStep c;
   c.need_mem = need_mem;
-#ifdef N2V_STATS
-  WaveStats WS;
-  for (int i = 0; i < 40; ++i) WS.v[i] = 0;
-  const unsigned long long t_kernel0 = __builtin_readcyclecounter();
-#endif
   for (;;) {
     uint32_t t = 0;
     if (lane == 0) t = atomicAdd(&status[1], 64u);
@@ -1442,9 +1364,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_LANES_WAVES) void walk_exa
       int64_t w_off = 0;
       int w_rpos = 0, w_nR = 0, w_nM = 0;
       bool w_ok = false;
-#ifdef N2V_STATS
-      const unsigned long long t_q0 = __builtin_readcyclecounter();
-#endif
       if (walking) {
         const uint64_t bits = step_bits(h0, (uint32_t)step);
         u1 = (uint32_t)(bits >> 32);
@@ -1465,7 +1384,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_LANES_WAVES) void walk_exa
         const bool counts_ok = step_biased && fR != N2V_EC_RETURN_SAT && fM != N2V_EC_SHARED_MASK;
         uint64_t wraw = 0;
         if (have_w && counts_ok && ((need_mem && fM > 0) || fR > 0)) {
-          N2V_CHECK_RANGE(3, e_prev, (int64_t)0, g.n_edges);
           wraw = g.wedge_off[e_prev];  // list offset | return position << 40
         }
         if (kHops) {
@@ -1487,7 +1405,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_LANES_WAVES) void walk_exa
             w_rpos = (int)(wraw >> N2V_WEDGE_RPOS_SHIFT);
             int lo_pick = 0;  // entries of the edge's list below `pick`
             if (need_mem && !isR && nM > 0) {  // :226
-              if (have_w && !(dbg & 4))
+              if (have_w)
                 lo_pick = wedge_lower(g.wedge_pos, w_off, nM, pick, w_wide, isM);
               else
                 isM = member_sorted_lane(g.col + sb, m, x);
@@ -1500,8 +1418,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_LANES_WAVES) void walk_exa
               const bool any_under = (nR && uR) || (nM && uM) || (nO && uO);
               const bool any_over = (nR && !uR) || (nM && !uM) || (nO && !uO);
               int jres = -1;
-              if (any_under && any_over && have_w && uO && !(nR && uR) && !(nM && uM) &&
-                  !(dbg & (16 | 4))) {
+              if (any_under && any_over && have_w && uO && !(nR && uR) && !(nM && uM)) {
                 // plain branches on the (uniform) list width: never a select between two loads
                 if (w_wide)
                   jres = lane_case_a_jump<uint32_t>(
@@ -1516,16 +1433,14 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_LANES_WAVES) void walk_exa
                 if (!(r2 < p_pick)) idx = 0;
               } else if (jres >= 0) {
                 idx = jres;  // closed form: no loop at all
-                N2V_CHECK_RANGE(7, idx, 0, n);
-              } else if (have_w && n <= 64 && !(dbg & 1)) {
+              } else if (have_w && n <= 64) {
                 // a short row: this lane replays the pairing itself from the two class masks
                 uint64_t Rm = 0ull, Mm = 0ull;
                 if (nR) Rm = ((nR >= 64) ? ~0ull : ((1ull << nR) - 1ull)) << w_rpos;
                 const uint64_t Mm_list = wedge_mask(g.wedge_pos, w_off, nM, w_wide);
                 Mm = Mm_list;
                 idx = lane_pairing(n, Rm, Mm, pick, r2, vR, vM, vO);
-                N2V_CHECK_RANGE(2, idx, 0, n);
-              } else if (have_w && uO && !(nR && uR) && !(nM && uM) && !(dbg & 8)) {
+              } else if (have_w && uO && !(nR && uR) && !(nM && uM)) {
                 // a longer row whose only underfull class is "other": still this lane's work
                 if (w_wide)
                   idx = lane_case_a<uint32_t>(n, pick, r2, vR, vM, vO, nR, w_rpos, nM,
@@ -1535,12 +1450,11 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_LANES_WAVES) void walk_exa
                   idx = lane_case_a<uint16_t>(n, pick, r2, vR, vM, vO, nR, w_rpos, nM,
                                               reinterpret_cast<const uint16_t *>(g.wedge_pos) + w_off,
                                               isR, isM, reinterpret_cast<uint16_t *>(L.cls), lane);
-                N2V_CHECK_RANGE(6, idx, 0, n);
               } else {
                 unresolved = true;
                 w_nR = nR;
                 w_nM = nM;
-                w_ok = have_w && !(dbg & 2);
+                w_ok = have_w;
               }
               if (!unresolved && idx != pick) {
                 if (kHops) {
@@ -1556,12 +1470,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_LANES_WAVES) void walk_exa
       }
       // the steps that need the pairing: the whole wave, one walker at a time
       uint64_t fb = ballot64(unresolved);
-#ifdef N2V_STATS
-      const unsigned long long t_f0 = __builtin_readcyclecounter();
-      WS.v[26] += t_f0 - t_q0;
-      WS.v[28] += __popcll(ballot64(walking));
-      WS.v[29] += __popcll(fb);
-#endif
       while (fb != 0ull) {
         const int l = (int)__builtin_ctzll(fb);
         fb &= fb - 1ull;
@@ -1586,26 +1494,12 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_LANES_WAVES) void walk_exa
         }
         const uint32_t u1_l = (uint32_t)__builtin_amdgcn_readlane((int)u1, l);
         const uint32_t u2_l = (uint32_t)__builtin_amdgcn_readlane((int)u2, l);
-#ifdef N2V_STATS
-        const unsigned long long t_d0 = __builtin_readcyclecounter();
-#endif
-        const int res = __builtin_amdgcn_readfirstlane(unit_draw<true>(c, K, u1_l, u2_l, lane, L N2V_STATS_PASS));
+        const int res = __builtin_amdgcn_readfirstlane(unit_draw<true>(c, K, u1_l, u2_l, lane, L));
         __builtin_amdgcn_wave_barrier();
         if (lane == l) {
           idx = res;
-          N2V_CHECK_RANGE(1, idx, 0, n);
         }
-#ifdef N2V_STATS
-        {  // fallback draws and their cycles by deg(v) bucket
-          const int bk = c.n <= 64 ? 0 : (c.n <= 1024 ? 1 : (c.n <= 4096 ? 2 : 3));
-          WS.v[32 + bk] += 1;
-          WS.v[36 + bk] += __builtin_readcyclecounter() - t_d0;
-        }
-#endif
       }
-#ifdef N2V_STATS
-      WS.v[27] += __builtin_readcyclecounter() - t_f0;
-#endif
       if (unresolved) {
         if (kHops) {
           h = load_hop(g.hops + vb + idx);
@@ -1644,11 +1538,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, N2V_LANES_WAVES) void walk_exa
       valid_out[r] = alive ? 1 : 0;
     }
   }
-#ifdef N2V_STATS
-  WS.v[23] = __builtin_readcyclecounter() - t_kernel0;
-  if (lane == 0)
-    for (int i = 0; i < 40; ++i) atomicAdd(&n2v_stats[i], WS.v[i]);
-#endif
 }
 
 }  // namespace n2v
@@ -1711,27 +1600,11 @@ extern "C" int n2v_edge_row_sums_build(const n2v_graph *g, double p, double q, c
 
 // returns 1 when the unit-weight kernel applies (and was launched), 0 when the caller
 // must use the generic kernel, < 0 on error
-// workspace n2v_walk_ws can use for (g, p, q): the record lists of n2v_walk_wedge2.hip, 0 = none
-extern "C" int64_t n2v_walk_exact_unit_workspace(const n2v_graph *g, int64_t total,
-                                                 int32_t walk_length, double p, double q) {
-  if (g->w != nullptr || g->w64 != nullptr || (p == 1.0 && q == 1.0)) return 0;
-  if (!g->hops || !g->wedge_off || !g->wedge_pos || (g->reserved & 1)) return 0;
-  n2v::UnitConsts K;
-  bool dyadic = false;
-  if (!unit_consts(p, q, K, dyadic) || !dyadic) return 0;
-  if (total <= 0 || total >= 0xffffff00ll || walk_length >= 0xfffff0) return 0;
-#ifdef N2V_WITH_WEDGE2
-  return n2v_walk_wedge2_workspace(total);
-#else
-  return 0;  // the passes over a workspace (n2v_walk_wedge2.hip) are not part of this build: `make WEDGE2=1`
-#endif
-}
-
 extern "C" int n2v_walk_exact_unit_try(const n2v_graph *g, const int32_t *start_ids,
                                        int64_t n_start, int32_t num_walks,
                                        int32_t walk_length, double p, double q, uint64_t seed,
                                        int32_t *walks_out, uint8_t *valid_out, uint32_t *status,
-                                       void *workspace, int64_t workspace_bytes, void *stream) {
+                                       void *stream) {
   if (g->w != nullptr || g->w64 != nullptr) return 0;
   n2v::UnitConsts K;
   bool dyadic = false;
@@ -1755,21 +1628,6 @@ extern "C" int n2v_walk_exact_unit_try(const n2v_graph *g, const int32_t *start_
   // (values that are not dyadic: the same kernel adds the row up in the reference's order and
   // replays every pairing run by run)
   if (!(p == 1.0 && q == 1.0) && !(g->reserved & 1)) {
-    // every per-edge table is at hand and the caller lent a workspace: closed forms in the main
-    // launches, declined steps replayed out of line (n2v_walk_wedge2.hip)
-#ifdef N2V_WITH_WEDGE2  // (measured slower than the one-launch kernel on every BASELINE graph: a build option)
-    if (workspace) {
-      int rounds = 4;
-      if (const char *e = getenv("N2V_WEDGE2_ROUNDS")) rounds = atoi(e);
-      const int r2 = n2v_walk_wedge2_try(g, start_ids, n_start, num_walks, walk_length, p, q, K, seed,
-                                         walks_out, valid_out, status, workspace, workspace_bytes,
-                                         rounds, stream);
-      if (r2 != 0) return r2;
-    }
-#else
-    (void)workspace;
-    (void)workspace_bytes;
-#endif
     // every per-edge table is at hand: the kernel in which no step needs the wave
     const int rw = n2v_walk_wedge_try(g, start_ids, n_start, num_walks, walk_length, p, q, K, seed,
                                       walks_out, valid_out, status, stream);
@@ -1852,13 +1710,3 @@ extern "C" int n2v_partition_step_unit_try(const int64_t *rowptr, const int32_t 
   return 1;
 }
 
-#ifdef N2V_STATS
-extern "C" int n2v_debug_stats_unit(unsigned long long *out_host, int reset) {
-  if (hipMemcpyFromSymbol(out_host, HIP_SYMBOL(n2v::n2v_stats), sizeof(unsigned long long) * 40) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[40] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(n2v::n2v_stats), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif

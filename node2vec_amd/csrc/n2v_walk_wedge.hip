@@ -26,12 +26,10 @@
 namespace n2v {
 
 constexpr int kWedgeThreads = 256;
-#ifndef N2V_WEDGE_WAVES
-#define N2V_WEDGE_WAVES 6
-#endif
+constexpr int kWedgeWaves = 6;
 
 template <int kMode>
-__global__ __launch_bounds__(kWedgeThreads, N2V_WEDGE_WAVES) void walk_exact_wedge_kernel(
+__global__ __launch_bounds__(kWedgeThreads, kWedgeWaves) void walk_exact_wedge_kernel(
     n2v_graph g, const int32_t *__restrict__ start_ids, int64_t n_start, int32_t num_walks,
     int32_t walk_length, double p, double q, UnitConsts K, uint64_t seed,
     int32_t *__restrict__ walks_out, uint8_t *__restrict__ valid_out,
@@ -51,9 +49,6 @@ __global__ __launch_bounds__(kWedgeThreads, N2V_WEDGE_WAVES) void walk_exact_wed
   const bool merge_r = K.bR == K.bO;
   constexpr bool kShared = kMode == 1 || kMode == 2;
   const bool base_aligned = (reinterpret_cast<uintptr_t>(walks_out) & 63u) == 0;
-#ifdef N2V_CHECK
-  n2v_check_status = status;
-#endif
 
   int64_t w0 = 0;  // absolute word index of path position 0 of the current walker
   int lo = 0;      // first word of the current sector that belongs to this row
@@ -132,14 +127,9 @@ __global__ __launch_bounds__(kWedgeThreads, N2V_WEDGE_WAVES) void walk_exact_wed
       // Steps whose edge has no shared neighbour need it only if the pairing runs (lazy).
       uint64_t wraw = 0;
       bool w_loaded = false;
-#ifdef N2V_ABLATE_W
-      const bool early_ok = N2V_ABLATE_W != 3;
-#else
-      const bool early_ok = true;
-#endif
+      const bool early_ok = true;  // (a timing-only build once cleared it; folded away, the compiler orders the prologue otherwise)
       // (not dyadic: the row sum needs the list and the return position at every step)
       if (counts_ok && ((need_mem && fM > 0) || ((kMode == 2 || (early_ok && always_pair)) && (fM > 0 || fR > 0)))) {
-        N2V_CHECK_RANGE(3, e_prev, (int64_t)0, g.n_edges);
         wraw = g.wedge_off[e_prev];
         w_loaded = true;
       }
@@ -200,7 +190,6 @@ __global__ __launch_bounds__(kWedgeThreads, N2V_WEDGE_WAVES) void walk_exact_wed
               if (!(r2 < p_pick)) idx = 0;
             } else {
               if (!w_loaded) {  // the return position (and an empty list)
-                N2V_CHECK_RANGE(3, e_prev, (int64_t)0, g.n_edges);
                 wraw = g.wedge_off[e_prev];
                 w_off = (int64_t)(wraw & N2V_WEDGE_OFF_MASK);
               }
@@ -224,11 +213,7 @@ __global__ __launch_bounds__(kWedgeThreads, N2V_WEDGE_WAVES) void walk_exact_wed
                                             reinterpret_cast<const uint16_t *>(g.wedge_pos) + w_off,
                                             isR, isM, lo_pick, reinterpret_cast<uint16_t *>(stage), lane);
               idx = res;
-              N2V_CHECK_RANGE(2, idx, 0, n);
             }
-#ifdef N2V_ABLATE_W
-            if (N2V_ABLATE_W == 2) idx = pick;  // timing-only: never a second gather
-#endif
             if (idx != pick) {
               h = load_hop(g.hops + vb + idx);
               x = h.col;
@@ -261,17 +246,13 @@ __global__ __launch_bounds__(kWedgeThreads, N2V_WEDGE_WAVES) void walk_exact_wed
 // is requested together with the hop entry and holds the return position and a short list itself,
 // so a step that needs its list is two INDEPENDENT gathers instead of hop + offset -> list.
 // kMode 0, 1, 3: dyadic p, q (values that are not keep the kernel above); 16-bit positions.
-#ifndef N2V_SLOTS_WAVES
-#define N2V_SLOTS_WAVES 6
-#endif
+constexpr int kSlotsWaves = 6;
 // Instances <1> (the return run shares a stack) and <2> (values that are not dyadic) carry the most code per
 // step; at six waves per SIMD (80 VGPRs) they spill 144 / 132 bytes per lane, at five (96 VGPRs) next to
 // nothing.  The kernel is bound by its sectors, not by its waves, so those two run at five.
-#ifndef N2V_SLOTS_WAVES_BIG
-#define N2V_SLOTS_WAVES_BIG 5
-#endif
+constexpr int kSlotsWavesBig = 5;
 template <int kMode>
-__global__ __launch_bounds__(kWedgeThreads, (kMode == 1 || kMode == 2) ? N2V_SLOTS_WAVES_BIG : N2V_SLOTS_WAVES)
+__global__ __launch_bounds__(kWedgeThreads, (kMode == 1 || kMode == 2) ? kSlotsWavesBig : kSlotsWaves)
 void walk_exact_wedge_slots_kernel(
     n2v_graph g, const int32_t *__restrict__ start_ids, int64_t n_start, int32_t num_walks,
     int32_t walk_length, double q, UnitConsts K, uint64_t seed, int32_t *__restrict__ walks_out,
@@ -284,15 +265,6 @@ void walk_exact_wedge_slots_kernel(
   const int64_t total = n_start * (int64_t)num_walks;
   const int L1 = walk_length + 1;
   const StepFlags F = step_flags(g, K, q);
-#ifdef N2V_NEAR_COUNT
-  n2v_count_words = status;
-#endif
-#if defined(N2V_BIG_STATS) && defined(N2V_BIG_DECLINES)
-  n2v_big_words = status;
-#endif
-#ifdef N2V_DECLINE_STATS
-  n2v_decline_words = status + 8;
-#endif
   const bool base_aligned = (reinterpret_cast<uintptr_t>(walks_out) & 63u) == 0;
 
   int64_t w0 = 0;  // absolute word index of path position 0 of the current walker
@@ -396,7 +368,7 @@ void walk_exact_wedge_slots_kernel(
 // N(s) nor a pass over N(v).  (The step is restated, not shared with the kernel above: that one's
 // registers are the flagship configuration's.)
 template <int kMode>
-__global__ __launch_bounds__(kWedgeThreads, N2V_WEDGE_WAVES) void partition_step_wedge_kernel(
+__global__ __launch_bounds__(kWedgeThreads, kWedgeWaves) void partition_step_wedge_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, int64_t lo, int64_t n_local,
     const int64_t *__restrict__ head, int head_cols, const int64_t *__restrict__ src_ptr,
     const int32_t *__restrict__ src_ids, int src_at, int64_t k, double p, double q, UnitConsts K,
@@ -412,9 +384,6 @@ __global__ __launch_bounds__(kWedgeThreads, N2V_WEDGE_WAVES) void partition_step
   const bool need_mem = q != 1.0;
   const bool merge_r = K.bR == K.bO;
   constexpr bool kShared = kMode == 1 || kMode == 2;
-#ifdef N2V_CHECK
-  n2v_check_status = status;
-#endif
   // whole waves stay in the loop (lane_case_a stages through the wave's LDS tile)
   const int64_t k_up = (k + 63) & ~(int64_t)63;
   for (int64_t i = (int64_t)blockIdx.x * kWedgeThreads + tid; i < k_up;
@@ -477,9 +446,7 @@ __global__ __launch_bounds__(kWedgeThreads, N2V_WEDGE_WAVES) void partition_step
             } else {
               // the closed forms on the values the counts give, with margins (n2v_unit_near.h), before
               // the row is added up in the reference's order
-              near_idx = N2V_NEAR_FORMS ? near_step<uint32_t>(n, pick, r2a, K, nR, w_rpos, nM, list, isR, isM,
-                                                              lo_pick, -1)
-                                        : -1;
+              near_idx = near_step<uint32_t>(n, pick, r2a, K, nR, w_rpos, nM, list, isR, isM, lo_pick, -1);
               avg = near_idx >= 0 ? approx : lane_row_sum<uint32_t>(n, K, nR, w_rpos, nM, list) / (double)n;
             }
           } else {
@@ -505,7 +472,6 @@ __global__ __launch_bounds__(kWedgeThreads, N2V_WEDGE_WAVES) void partition_step
               else if (kShared && uO && nR && !uR && nM && uM) arr = 5;
               idx = pair_listed<uint32_t, kMode>(arr, n, pick, r2, K, avg, nR, w_rpos, nM, list, isR,
                                                  isM, lo_pick, stage, lane);
-              N2V_CHECK_RANGE(2, idx, 0, n);
             }
           }
         }

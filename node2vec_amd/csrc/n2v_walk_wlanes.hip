@@ -46,7 +46,7 @@
 
 namespace n2v {
 
-// Two instances: rows of up to N2V_WLANES_SHORT slots in groups of 8 (blocks of 256 lanes, 4 waves
+// Two instances: rows of up to kWlanesShort slots in groups of 8 (blocks of 256 lanes, 4 waves
 // per SIMD); longer rows in groups of 32 (blocks of 64 lanes): a lane reads its row group by group and
 // each group is a round trip to memory that nothing hides but the next group's load, so on a row of
 // 10^4 - 10^5 slots the group must be long (8-slot groups: 75 ms per step for the wave that stands on
@@ -107,11 +107,7 @@ struct WlList {
     R = &row;
     win = nxt = 0ull;
     have_nxt = 0;
-#if defined(N2V_WL_ABLATE) && (N2V_WL_ABLATE & 2)  // timing only: no shared positions
-    const int n = 0;
-#else
     const int n = row.first ? 0 : row.nM;
-#endif
     idx = kFwd ? 0 : n - 1;
     if (n == 0) {
       cur = kFwd ? 0x7fffffff : -1;
@@ -186,11 +182,6 @@ struct WlRaw {
 template <typename WT, int CH>
 __device__ __forceinline__ WlRaw<WT, CH> wl_load_raw(const WT *w, int c0, int n) {
   WlRaw<WT, CH> out;
-#if defined(N2V_WL_ABLATE) && (N2V_WL_ABLATE & 1)  // timing only: no weight loads
-#pragma unroll
-  for (int k = 0; k < CH; ++k) out.v[k] = (WT)(1 + ((c0 + k) & 3));
-  return out;
-#endif
   if (c0 + CH <= n) {
     // whole group inside the row: wide loads (dword-aligned only: rows start anywhere)
     struct __attribute__((packed, aligned(4))) Pack {
@@ -256,17 +247,11 @@ __device__ __forceinline__ void wl_refill(WlCursor<WT, CH> &C, const WlRow &R, c
 }
 
 // index sampling_from_alias(r1, r2) returns on the table of this row, or -1: ZeroDivisionError (:172-173)
-#ifdef N2V_WL_STATS  // diagnostic build: the longest sum pass / pairing of a launch (cycles >> 8) and its row
-__device__ uint32_t *wl_stats_words;
-#endif
 
 template <typename WT, int CH, int TH, bool kPow2>
 __device__ __forceinline__ int wl_draw(const WlRow &R, const WT *w, const WlConsts &K, int pick, double r2,
                                        double *tU, double *tO, int tid) {
   const int n = R.n;
-#ifdef N2V_WL_STATS
-  const unsigned long long st0 = __builtin_readcyclecounter();
-#endif
   // ---- the row sum in the reference's order (:172) -----------------------------------------------
   double total = 0.0, b_pick = 0.0;
   double bmin = __builtin_huge_val(), bmax = -__builtin_huge_val();
@@ -297,10 +282,6 @@ __device__ __forceinline__ int wl_draw(const WlRow &R, const WT *w, const WlCons
       }
     }
   }
-#ifdef N2V_WL_STATS
-  const unsigned long long st1 = __builtin_readcyclecounter();
-  atomicMax(wl_stats_words + 2, (uint32_t)((st1 - st0) >> 8));
-#endif
   const double avg = total / (double)n;  // :172
   if (avg == 0.0) return -1;
   const double p_pick = b_pick / avg;    // :173
@@ -374,13 +355,6 @@ __device__ __forceinline__ int wl_draw(const WlRow &R, const WT *w, const WlCons
     }
     if (finished) break;
   }
-#ifdef N2V_WL_STATS
-  {
-    const uint32_t dt = (uint32_t)((__builtin_readcyclecounter() - st1) >> 8);
-    const uint32_t old = atomicMax(wl_stats_words + 3, dt);
-    if (dt > old) wl_stats_words[1] = (uint32_t)n;  // (racy: the row of a longest pairing)
-  }
-#endif
   return (r2 < fin_prob) ? pick : fin_alias;  // :95-99
 }
 
@@ -395,9 +369,6 @@ __global__ __launch_bounds__(TH) void walk_weighted_step_kernel(
   const int tid = threadIdx.x;
   const int L1 = walk_length + 1;
   const bool biased = !(K.p == 1.0 && K.q == 1.0);
-#ifdef N2V_WL_STATS
-  wl_stats_words = status;
-#endif
   for (int64_t i = (int64_t)blockIdx.x * TH + tid; i < n_rows; i += (int64_t)gridDim.x * TH) {
     const int64_t r = order ? order[i] : i;
     if (r < 0 || r >= n_rows) {
@@ -497,10 +468,7 @@ constexpr int kWmUndecided = -2;
 // 2 and 8 blocks measured the same, profiles/r8y_wm_variants.log), more blocks per entry on rows of more than
 // 128 x 1 024 slots
 constexpr int kWmEntries = 128;
-#ifndef N2V_WM_MIN_BLOCKS_PER_ENTRY
-#define N2V_WM_MIN_BLOCKS_PER_ENTRY 4
-#endif
-constexpr int kWmMinBlocksPerEntry = N2V_WM_MIN_BLOCKS_PER_ENTRY;
+constexpr int kWmMinBlocksPerEntry = 4;
 struct WmLds {
   double cd[kWmEntries], cx[kWmEntries];  // sum of d / of x = probs - 1 over the slots up to the end of entry i
   int lm0[kWmEntries];                    // how many shared positions lie below the first slot of entry i
@@ -1014,9 +982,6 @@ __device__ __forceinline__ int wm_decide(const WlRow &R, const WT *w, const WlCo
   double M = kfac * 16.0 * nn * nn * eps;
   const double p_pick = b_pick * inv;
   const bool under = p_pick < 1.0 - 2.0 * delta;
-#if defined(N2V_WM_ABLATE) && N2V_WM_ABLATE == 1  // timing only: the walk ends with the row sum
-  return pick;
-#endif
   if (!under && !(p_pick > 1.0 + 2.0 * delta)) return kWmUndecided;
   if (under) {
     if (r2 < p_pick * (1.0 - delta)) return pick;  // an underfull slot keeps its probs: accepted
@@ -1091,9 +1056,6 @@ __device__ __forceinline__ int wm_decide(const WlRow &R, const WT *w, const WlCo
   if (!summaries) below = wm_wave_sum(under ? pre_d : pre_x + pre_d);
   if (exact_total)  // (+ 64: a block summary is the difference of two sums of up to 256 weights)
     M = 8.0 * eps * (nn * (w_max * cmax * inv + 12.0 + 64.0) + (nn * (1.0 / 256.0) + 16.0) * (4.0 * tot_d + 4.0));
-#if defined(N2V_WM_ABLATE) && N2V_WM_ABLATE == 2  // timing only: the walk ends with the pass over the row
-  return below > 1.0e300 ? 0 : pick;
-#endif
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   const double x_pick = p_pick - 1.0;
@@ -1325,11 +1287,9 @@ __device__ __forceinline__ int lm_draw(const WlRow &R, const WT *w, const WlCons
   return lm_next_over_below<WT, kPow2>(R, K, w, inv, delta, pick, x_t);
 }
 
-#ifndef N2V_LM_WAVES_PER_SIMD
-#define N2V_LM_WAVES_PER_SIMD 6
-#endif
+constexpr int kLmWavesPerSimd = 6;
 template <typename WT, bool kPow2>
-__global__ __launch_bounds__(256, N2V_LM_WAVES_PER_SIMD) void walk_weighted_lane_margin_kernel(
+__global__ __launch_bounds__(256, kLmWavesPerSimd) void walk_weighted_lane_margin_kernel(
     n2v_graph g, const WT *__restrict__ w, const int32_t *__restrict__ start_ids, int32_t num_walks,
     const int64_t *__restrict__ order, int64_t n_rows, int32_t max_n, int32_t step, int32_t walk_length,
     WlConsts K, uint64_t seed, int64_t *__restrict__ edge_state, int32_t *__restrict__ walks,
@@ -1410,12 +1370,10 @@ __global__ __launch_bounds__(256, N2V_LM_WAVES_PER_SIMD) void walk_weighted_lane
 }
 
 constexpr int kWmWaves = 4;
-#ifndef N2V_WM_WAVES_PER_SIMD
-#define N2V_WM_WAVES_PER_SIMD 5
-#endif
+constexpr int kWmWavesPerSimd = 5;
 
 template <typename WT, bool kPow2, bool kSeq>
-__global__ __launch_bounds__(kWmWaves * 64, N2V_WM_WAVES_PER_SIMD) void walk_weighted_margin_kernel(
+__global__ __launch_bounds__(kWmWaves * 64, kWmWavesPerSimd) void walk_weighted_margin_kernel(
     n2v_graph g, const WT *__restrict__ w, const int32_t *__restrict__ start_ids, int32_t num_walks,
     const int64_t *__restrict__ order, int64_t n_rows, int32_t min_n, int32_t step, int32_t walk_length,
     WlConsts K, uint64_t seed, int64_t *__restrict__ edge_state, int32_t *__restrict__ walks,
@@ -1540,13 +1498,9 @@ extern "C" int n2v_weighted_step_wave_launch(const n2v_graph *g, const int32_t *
 // cfg 2 (profiles/r7h_time_wlanes_two_instances.log, r7k_time_wlanes.log): the 32-slot instance (255 VGPRs,
 // one wave per SIMD) LOSES -- 15 - 25 M steps/s with the cut at 1 024 / 4 096 slots against 51 - 55 M with
 // every row in the 8-slot instance -- and so does a whole wave per walker on the long rows (37 - 47 M), so the
-// default sends every row to the 8-slot instance; the other two stay as build-time variants.
-#ifndef N2V_WLANES_SHORT
-#define N2V_WLANES_SHORT 0x7fffffff
-#endif
-#ifndef N2V_WLANES_WAVE_FROM
-#define N2V_WLANES_WAVE_FROM 0x7fffffff
-#endif
+// default sends every row to the 8-slot instance; the other two stay behind these two cuts.
+constexpr int kWlanesShort = 0x7fffffff;
+constexpr int kWlanesWaveFrom = 0x7fffffff;
 
 namespace n2v {
 template <typename WT, int CH, int TH>
@@ -1574,21 +1528,10 @@ static int wl_launch(const n2v_graph *g, const WT *w, const int32_t *start_ids, 
 
 // rows of at least this many slots: a wave per walker that decides the pairing with margins
 // (walk_weighted_margin_kernel), given an order and a scratch list for the walkers it leaves undecided
-#ifndef N2V_WLANES_MARGIN_FROM
-#define N2V_WLANES_MARGIN_FROM 768
-#endif
-// small batches: the cut is n_rows / this, at least N2V_WLANES_MARGIN_FROM_MIN
-#ifndef N2V_WLANES_WALKERS_PER_CUT_SLOT
-#define N2V_WLANES_WALKERS_PER_CUT_SLOT 2048
-#endif
-#ifndef N2V_WLANES_MARGIN_FROM_MIN
-#define N2V_WLANES_MARGIN_FROM_MIN 48
-#endif
-// the rows below that: 1 = the same decision with a lane per walker (walk_weighted_lane_margin_kernel), 0 = the
-// exact lane kernel (the pairing replayed: round 5's first form)
-#ifndef N2V_WLANES_LANE_MARGINS
-#define N2V_WLANES_LANE_MARGINS 1
-#endif
+constexpr int kWlanesMarginFrom = 768;
+// small batches: the cut is n_rows / this, at least kWlanesMarginFromMin
+constexpr int kWlanesWalkersPerCutSlot = 2048;
+constexpr int kWlanesMarginFromMin = 48;
 
 namespace n2v {
 template <typename WT, bool kSeq>
@@ -1703,13 +1646,12 @@ extern "C" int n2v_walk_weighted_step(const n2v_graph *g, const int32_t *start_i
   }
   hipStream_t st = (hipStream_t)stream;
   // Without an order every row is the 8-slot instance's.  With one (rows sorted by the length of the row
-  // stood on, descending): the rows above N2V_WLANES_SHORT slots first, in 32-slot groups; a whole wave per
-  // walker for the rows from N2V_WLANES_WAVE_FROM slots on (both off by default: see above).
-  const int short_n = order ? N2V_WLANES_SHORT : 0x7fffffff;
-  const int wave_from = order ? N2V_WLANES_WAVE_FROM : 0x7fffffff;
+  // stood on, descending): the rows above kWlanesShort slots first, in 32-slot groups; a whole wave per
+  // walker for the rows from kWlanesWaveFrom slots on (both off by default: see above).
+  const int short_n = order ? kWlanesShort : 0x7fffffff;
+  const int wave_from = order ? kWlanesWaveFrom : 0x7fffffff;
   int rc = N2V_OK;
-  int lanes_max = 0x7fffffff;  // the lane kernel's rows: up to this many slots
-  if (order && scratch && row_sums && N2V_WLANES_MARGIN_FROM > 1) {
+  if (order && scratch && row_sums && kWlanesMarginFrom > 1) {
     // long rows first (the order is by row length, descending): a wave per walker, the pairing decided with
     // margins; scratch[0] = how many walkers it left undecided, scratch[1 ..] = those, -1 behind the last:
     // the exact wave kernel steps them
@@ -1717,12 +1659,12 @@ extern "C" int n2v_walk_weighted_step(const n2v_graph *g, const int32_t *start_i
     // at 768 slots whatever the batch), a wave ~700 vector instructions per walker.  A full batch (millions of walkers)
     // is throughput-bound and best at 768 (profiles/r8k_wm_cut.log); a small one is bound by that critical path, so the
     // cut comes down with the number of walkers (profiles/r10i_wm_cut_by_batch.log).  hubs->lane_cut > 0 overrides.
-    int from = N2V_WLANES_MARGIN_FROM;
+    int from = kWlanesMarginFrom;
     if (hubs && hubs->lane_cut > 0) {
       from = hubs->lane_cut;
     } else {
-      const int64_t by_batch = n_rows / N2V_WLANES_WALKERS_PER_CUT_SLOT;
-      if (by_batch < from) from = by_batch < N2V_WLANES_MARGIN_FROM_MIN ? N2V_WLANES_MARGIN_FROM_MIN : (int)by_batch;
+      const int64_t by_batch = n_rows / kWlanesWalkersPerCutSlot;
+      if (by_batch < from) from = by_batch < kWlanesMarginFromMin ? kWlanesMarginFromMin : (int)by_batch;
     }
     // scratch: two lists of n_rows + 2 words each -- [0] how many, [1 ..] the rows, -1 behind the last: what the
     // first launch (row sum in any order: general margins unless the sum is exact anyway) leaves undecided, and
@@ -1747,14 +1689,13 @@ extern "C" int n2v_walk_weighted_step(const n2v_graph *g, const int32_t *start_i
                                                walk_length, K, seed, edge_state, walks, valid, status, second, row_sums,
                                                hb, st);
     if (rc != N2V_OK) return rc;
-#if N2V_WLANES_LANE_MARGINS
-    // the rows below the cut: the same decision, a lane per walker (its undecided walkers join the list)
+    // the rows below the cut: the same decision, a lane per walker (its undecided walkers join the list; round 5's
+    // first form gave them to the exact lane kernel, the pairing replayed)
     rc = g->w64 ? n2v::lm_launch<double>(g, g->w64, start_ids, num_walks, order, n_rows, from - 1, step, walk_length, K,
                                          seed, edge_state, walks, valid, status, second, row_sums, st)
                 : n2v::lm_launch<float>(g, g->w, start_ids, num_walks, order, n_rows, from - 1, step, walk_length, K,
                                         seed, edge_state, walks, valid, status, second, row_sums, st);
     if (rc != N2V_OK) return rc;
-#endif
     rc = g->w64 ? n2v::wm_launch<double, true>(g, g->w64, start_ids, num_walks, second + 1, n_rows, 0, step,
                                                walk_length, K, seed, edge_state, walks, valid, status, last, row_sums,
                                                hb, st)
@@ -1765,10 +1706,7 @@ extern "C" int n2v_walk_weighted_step(const n2v_graph *g, const int32_t *start_i
     rc = n2v_weighted_step_wave_launch(g, start_ids, num_walks, last + 1, n_rows, -1, step, walk_length,
                                        return_param, inout_param, seed, edge_state, walks, valid, status, stream);
     if (rc != N2V_OK) return rc;
-#if N2V_WLANES_LANE_MARGINS
     return N2V_OK;  // (every row was one of the two margin kernels')
-#endif
-    lanes_max = from - 1;
   } else if (order && wave_from != 0x7fffffff) {
     if (hipMemsetAsync(status + 1, 0, sizeof(uint32_t), st) != hipSuccess) return N2V_ELAUNCH;
     rc = n2v_weighted_step_wave_launch(g, start_ids, num_walks, order, n_rows, wave_from - 1, step, walk_length,
@@ -1780,16 +1718,14 @@ extern "C" int n2v_walk_weighted_step(const n2v_graph *g, const int32_t *start_i
       rc = n2v::wl_launch<double, 32, 64>(g, g->w64, start_ids, num_walks, order, n_rows, short_n, wave_from - 1,
                                           step, walk_length, K, seed, edge_state, walks, valid, status, st);
     if (rc == N2V_OK)
-      rc = n2v::wl_launch<double, 8, 256>(g, g->w64, start_ids, num_walks, order, n_rows, 0,
-                                          short_n < lanes_max ? short_n : lanes_max, step,
+      rc = n2v::wl_launch<double, 8, 256>(g, g->w64, start_ids, num_walks, order, n_rows, 0, short_n, step,
                                           walk_length, K, seed, edge_state, walks, valid, status, st);
   } else {
     if (order && short_n != 0x7fffffff)
       rc = n2v::wl_launch<float, 32, 64>(g, g->w, start_ids, num_walks, order, n_rows, short_n, wave_from - 1,
                                          step, walk_length, K, seed, edge_state, walks, valid, status, st);
     if (rc == N2V_OK)
-      rc = n2v::wl_launch<float, 8, 256>(g, g->w, start_ids, num_walks, order, n_rows, 0,
-                                         short_n < lanes_max ? short_n : lanes_max, step,
+      rc = n2v::wl_launch<float, 8, 256>(g, g->w, start_ids, num_walks, order, n_rows, 0, short_n, step,
                                          walk_length, K, seed, edge_state, walks, valid, status, st);
   }
   return rc;

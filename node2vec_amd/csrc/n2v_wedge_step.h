@@ -1,29 +1,13 @@
 // n2v_wedge_step.h -- one step of an exact biased walk on a unit-weight graph from the per-edge
 // tables (hop table with class counts + wedge table, include/n2v_hip.h), by one lane: shared by the
-// kernels of n2v_walk_wedge.hip (one launch, replays inline) and n2v_walk_wedge2.hip (closed
-// forms in the main launches, declined steps replayed out of line).  Reference: the table
+// kernels of n2v_walk_wedge.hip (one launch, replays inline).  Reference: the table
 // generate_edge_alias_tables builds at (s, v) and sampling_from_alias on it, randomwalk.py:86-99,
 // :157-232.
 #pragma once
 #include "n2v_unit_core.h"
 #include "n2v_unit_near.h"
 
-#ifndef N2V_DEFER_HOP
-#define N2V_DEFER_HOP 2  // 0: every step gathers the hop entry of `pick` first (rounds 4 - 5); 1: deferred on edges
-                         // with an inline return position only (A/B builds: profiles/r10o_time_defer_hop_ab.log)
-#endif
-#ifndef N2V_NEAR_FORMS
-#define N2V_NEAR_FORMS 1  // 0: values that are not dyadic replay every pairing (rounds 2 - 3; A/B builds)
-#endif
-
 namespace n2v {
-
-#ifdef N2V_NEAR_COUNT
-__device__ uint32_t *n2v_count_words;  // = status of the launch (set by the kernel's first lines)
-#endif
-#if defined(N2V_BIG_STATS) && defined(N2V_BIG_DECLINES)
-__device__ uint32_t *n2v_big_words;
-#endif
 
 // the pairing loop for slot `pick` by one lane: closed form by arrangement `arr` (see the kernel),
 // else -- fp64 rounding decides the draw: a tie or a thin margin -- the replays.
@@ -54,40 +38,14 @@ __device__ __forceinline__ int pair_listed(int arr, int n, int pick, double r2, 
     else if (arr == 5)
       res = lane_case_a3_jump<P>(n, pick, r2, K, nR, rpos, nM, isR, isM, lo_pick);
   }
-#ifdef N2V_ABLATE_W
-  if (N2V_ABLATE_W == 1 && arr == 2) res = pick;  // timing-only: no closed form at all
-#endif
-#ifdef N2V_NEAR_COUNT  // diagnostic build: pairings ([2]) / pairings the closed forms declined ([3])
-  if (kMode != 2) {
-    atomicAdd(n2v_count_words + 2, 1u);
-    if (res < 0) atomicAdd(n2v_count_words + 3, 1u);
-  }
-#endif
-#if defined(N2V_BIG_STATS) && defined(N2V_BIG_DECLINES)  // diagnostic: [2] then counts the big-row pairings the closed forms DECLINED
-  if (n >= N2V_BIG_STATS && res < 0) atomicAdd(n2v_big_words + 2, 1u);
-#endif
-#ifdef N2V_DECLINE_STATS  // diagnostic: declined pairings on rows of more than 64 / of 4096 slots and more, by arrangement
-  if (res < 0 && n > 64) atomicAdd(n2v_decline_words + 24 + arr, 1u);
-  if (res < 0 && n >= 4096) atomicAdd(n2v_decline_words + 56 + arr, 1u);
-  if (n > 64) atomicAdd(n2v_decline_words + 30, 1u);  // pairings on such rows
-  if (n >= 4096) atomicAdd(n2v_decline_words + 62, 1u);
-#endif
-#ifdef N2V_FORCE_REPLAY  // test build: every pairing on a row of more than 64 slots is REPLAYED (the closed forms unused)
-  res = -1;
-#endif
   if (res >= 0) return res;
-#ifdef N2V_ABLATE_STEP  // timing only: 4 = a pairing the closed forms decline keeps `pick` (no replay); 5 = on rows > 64
-  if (N2V_ABLATE_STEP == 4 || (N2V_ABLATE_STEP == 5 && n > 64)) return pick;
-#endif
   if constexpr (kMode == 2) {
     // a long row whose values are not dyadic: the closed forms on the reference's own values (the exact
     // row sum has been taken), with a margin that grows with n instead of n^2
-#ifndef N2V_FORCE_REPLAY
-    if (N2V_NEAR_FORMS && n >= kNearExactMin && arr >= 1) {
+    if (n >= kNearExactMin && arr >= 1) {
       res = near_listed_exact<P>(arr, n, pick, r2, K, avg, nR, rpos, nM, list, isR, isM, lo_pick, below);
       if (res >= 0) return res;
     }
-#endif
   }
   const double vR = K.bR / avg, vM = K.bM / avg, vO = K.bO / avg;
   if (n <= 64) {  // a short row: the two stacks as bit masks
@@ -96,20 +54,8 @@ __device__ __forceinline__ int pair_listed(int arr, int n, int pick, double r2, 
     const uint64_t Mm = wedge_mask_l<P>(list, nM);
     return lane_pairing(n, Rm, Mm, pick, r2, vR, vM, vO);
   }
-#ifdef N2V_DECLINE_STATS  // diagnostic: the cycles / 256 of the replays of long rows, and their number, by the length of the
-  // list (words 64 + 2 b, 65 + 2 b of the decline words; b = 0: <= 64 entries, 1: <= 256, 2: <= 1024, 3: <= 4096, 4: more)
-  const unsigned long long rep_t0 = __builtin_readcyclecounter();
-  auto timed = [&](int result) -> int {
-    const int b = nM <= 64 ? 0 : nM <= 256 ? 1 : nM <= 1024 ? 2 : nM <= 4096 ? 3 : 4;
-    atomicAdd(n2v_decline_words + 64 + 2 * b, (uint32_t)((__builtin_readcyclecounter() - rep_t0) >> 8));
-    atomicAdd(n2v_decline_words + 65 + 2 * b, 1u);
-    return result;
-  };
-#else
-  auto timed = [&](int result) -> int { return result; };
-#endif
-  if (arr == 1) return timed(lane_case_a<P>(n, pick, r2, vR, vM, vO, nR, rpos, nM, list, isR, isM, stage, lane));
-  if (arr == 2) return timed(lane_case_b<P>(n, pick, r2, vR, vM, vO, nR, rpos, nM, list, isR, isM, lo_pick, below));
+  if (arr == 1) return lane_case_a<P>(n, pick, r2, vR, vM, vO, nR, rpos, nM, list, isR, isM, stage, lane);
+  if (arr == 2) return lane_case_b<P>(n, pick, r2, vR, vM, vO, nR, rpos, nM, list, isR, isM, lo_pick, below);
   if constexpr (kShared) {
     if (arr == 3) return lane_case_a2<P>(n, pick, r2, vR, vM, vO, nR, rpos, nM, list, isR, isM, stage, lane);
     if (arr == 4) return lane_case_b2<P>(n, pick, r2, vR, vM, vO, nR, rpos, nM, list, isR, isM);
@@ -180,15 +126,11 @@ __device__ __forceinline__ int wedge_step(const n2v_graph &g, const UnitConsts &
                                           uint32_t *stage, int lane, uint32_t *status,
                                           uint16_t *lds_list = nullptr);
 
-// the step of a walker standing on a WIDE row of a mixed wedge table, out of line (N2V_WIDE_NOINLINE):
+// the step of a walker standing on a WIDE row of a mixed wedge table (out of line it was measured no faster):
 // it is taken by a few per cent of the steps at most, and inlined into the slots kernel its 32-bit
 // instances of the closed forms cost every step registers (scratch 24 -> 40 B per lane in <0>, 100 -> 144 in <1>)
 template <int kMode, bool kJumpOnly>
-#ifdef N2V_WIDE_NOINLINE
-__device__ __attribute__((noinline)) int
-#else
 __device__ __forceinline__ int
-#endif
 wedge_step_wide(const n2v_graph &g, const UnitConsts &K, const StepFlags &F, uint32_t u1, uint32_t u2, int32_t s,
                 int64_t vb, int n, int64_t e_prev, uint32_t ec_prev, n2v_hop &h, uint32_t *stage, int lane,
                 uint32_t *status) {
@@ -211,11 +153,6 @@ __device__ __forceinline__ int wedge_step(const n2v_graph &g, const UnitConsts &
     // uint32 lists and no slot -- the step of a walker standing on such a row goes through wedge_off
     // (a per-lane branch: the other lanes of the wave keep their slots)
     if (g.wedge_wide >= 2 && n >= g.wedge_wide) {
-#if defined(N2V_ABLATE_WIDE) && N2V_ABLATE_WIDE == 1  // timing only: a wide step is a plain uniform draw
-      const int pk = pick_index(u1, n);
-      h = load_hop(g.hops + vb + pk);
-      return pk;
-#endif
       // (round 6) a wide row: its edges have FOLDED lists and slots (ListRef, n2v_wedge_slots_fold) and it takes the
       // step below like every other row.  (The launcher gives a mixed table without folded slots to the kernel that
       // reads wedge_off; rounds 4 - 5 stepped such a row here through a second, 32-bit instance of this function,
@@ -285,14 +222,15 @@ __device__ __forceinline__ int wedge_step(const n2v_graph &g, const UnitConsts &
   // needs in registers already -- the return run is the slots [rpos, rpos + nR), every other slot is "other" -- so the
   // hop entry of `pick` is not a gather the step has to wait for, and when the draw returns another slot it was a
   // gather for nothing (a fifth of the steps at (0.5, 2), most of them where "other" is overfull).  Such a step
-  // decides first and gathers the entry of its RESULT: one gather, always.  (N2V_DEFER_HOP 0: rounds 4 - 5.)
-  // N2V_DEFER_HOP 2 (the default): also the steps that have asked for their slot -- the hop entry then waits for the
+  // decides first and gathers the entry of its RESULT: one gather, always.  (Rounds 4 - 5 gathered the entry of `pick`
+  // first at every step.)  So do the steps that have asked for their slot -- the hop entry then waits for the
   // slot, two dependent gathers where there were two parallel ones, and that costs nothing: the kernel is bound by
-  // the NUMBER of random sectors, not by their latency (+2 - 3.5 % over 1 on every (p, q), two runs).
+  // the NUMBER of random sectors, not by their latency (+2 - 3.5 % over deferring on `inl` edges only, on every
+  // (p, q), two runs: profiles/r10o_time_defer_hop_ab.log).
   // (A list that is not inside the slot is searched in memory, a chain of dependent probes: there the entry of `pick`
   // is requested at once, as before, and arrives behind them -- waiting with it cost the graph trimmed at the
   // reference's cap, whose hub steps are such searches, 10 %: 14.0 -> 12.6 G.)
-  const bool defer = N2V_DEFER_HOP && (inl || (N2V_DEFER_HOP == 2 && kSlots && w_loaded && fM <= (uint32_t)kSlotShort));
+  const bool defer = inl || (kSlots && w_loaded && fM <= (uint32_t)kSlotShort);
   if (!defer) h = load_hop(g.hops + vb + pick);
   if (!counts_ok) {
     atomicOr(status, N2V_ST_RANGE);
@@ -305,10 +243,6 @@ __device__ __forceinline__ int wedge_step(const n2v_graph &g, const UnitConsts &
   const bool isR = defer ? (nR > 0 && pick >= rp0 && pick < rp0 + nR) : (!F.merge_r && h.col == s);
   bool isM = false;
   int lo_pick = 0;  // entries of the edge's list below `pick`
-#ifdef N2V_ABLATE_STEP  // timing only: 1 = no search of a list that is not inside its slot
-  if (N2V_ABLATE_STEP == 1 && nM > kSlotShort) {
-  } else
-#endif
   if (F.need_mem && !isR && nM > 0) {  // :226
     if constexpr (kSlots)
       lo_pick = slot_lower(sa, sb, nM, pick, reinterpret_cast<const uint16_t *>(g.wedge_pos), isM, slot_nlow(),
@@ -333,16 +267,13 @@ __device__ __forceinline__ int wedge_step(const n2v_graph &g, const UnitConsts &
       // (round 4) Before the row is added up in the reference's order: the closed forms on the values
       // the COUNTS give, with margins (near_step, n2v_unit_near.h).  Anything closer than the margin
       // goes on to the exact row sum and the replays below.
-#ifdef N2V_NEAR_COUNT
-      atomicAdd(status + 2, 1u);
-#endif
       if constexpr (kSlots) {
         if (!w_loaded) {  // an edge without shared neighbours whose step got here: its return position
           sa = reinterpret_cast<const int4 *>(slot)[0];
           sb = reinterpret_cast<const int4 *>(slot)[1];
           w_loaded = true;
         }
-        if (N2V_NEAR_FORMS) {
+        {
           const uint16_t *nlist = slot + 2;
           if (nM > kSlotShort)
             nlist = reinterpret_cast<const uint16_t *>(g.wedge_pos) +
@@ -354,15 +285,6 @@ __device__ __forceinline__ int wedge_step(const n2v_graph &g, const UnitConsts &
             if (defer || res != pick) h = load_hop(g.hops + vb + res);
             return res;
           }
-#ifdef N2V_NEAR_COUNT  // diagnostic build: steps past the quick accept ([2]) / declined by the closed forms ([3])
-          atomicAdd(status + 3, 1u);
-#endif
-#ifdef N2V_ABLATE_STEP  // timing only: 6 = a step the closed forms with margins decline keeps `pick` (no row sum, no replay)
-          if (N2V_ABLATE_STEP == 6 || (N2V_ABLATE_STEP == 7 && n >= 4096)) {
-            h = load_hop(g.hops + vb + pick);
-            return pick;
-          }
-#endif
         }
         if (g.row_sums != nullptr && n >= g.row_sums_from) {
           // a long row: the sum of this edge's table was added up once (n2v_edge_row_sums_build: this routine, these bits)
@@ -395,17 +317,15 @@ __device__ __forceinline__ int wedge_step(const n2v_graph &g, const UnitConsts &
         }
         const int rp = (int)(wraw >> N2V_WEDGE_RPOS_SHIFT);
         int res = -1;
-        if (N2V_NEAR_FORMS) {
-          if (w_wide)
-            res = near_step<uint32_t>(n, pick, r2, K, nR, rp, nM,
-                                      reinterpret_cast<const uint32_t *>(g.wedge_pos) + w_off, isR, isM, lo_pick, -1);
-          else
-            res = near_step<uint16_t>(n, pick, r2, K, nR, rp, nM,
-                                      reinterpret_cast<const uint16_t *>(g.wedge_pos) + w_off, isR, isM, lo_pick, -1);
-          if (res >= 0) {
-            if (res != pick) h = load_hop(g.hops + vb + res);
-            return res;
-          }
+        if (w_wide)
+          res = near_step<uint32_t>(n, pick, r2, K, nR, rp, nM,
+                                    reinterpret_cast<const uint32_t *>(g.wedge_pos) + w_off, isR, isM, lo_pick, -1);
+        else
+          res = near_step<uint16_t>(n, pick, r2, K, nR, rp, nM,
+                                    reinterpret_cast<const uint16_t *>(g.wedge_pos) + w_off, isR, isM, lo_pick, -1);
+        if (res >= 0) {
+          if (res != pick) h = load_hop(g.hops + vb + res);
+          return res;
         }
         double sum;
         if (g.row_sums != nullptr && n >= g.row_sums_from)
@@ -420,28 +340,12 @@ __device__ __forceinline__ int wedge_step(const n2v_graph &g, const UnitConsts &
   } else {
     const int64_t isum = (int64_t)nR * K.TR + (int64_t)nM * K.TM + (int64_t)nO * K.TO;
     avg = ((double)isum * (1.0 / 1048576.0)) / (double)n;
-#if defined(N2V_ABLATE_STEP) && N2V_ABLATE_STEP == 8  // timing only: neither division of the quick path (with 2: no pairing either)
-    avg = ((double)isum * (1.0 / 1048576.0)) * 1e-3;
-#endif
   }
-#if defined(N2V_ABLATE_STEP) && N2V_ABLATE_STEP == 8
-  const double p_pick = pick3(isR, isM, K.bR, K.bM, K.bO) * 0.9 + avg * 1e-30;
-#else
   const double p_pick = pick3(isR, isM, K.bR, K.bM, K.bO) / avg;  // :173
-#endif
   if (p_pick < 1.0 && r2 < p_pick) {  // an accepted underfull slot is final
     if (defer) h = load_hop(g.hops + vb + idx);
     return idx;
   }
-#if defined(N2V_ABLATE_WIDE) && N2V_ABLATE_WIDE == 2  // timing only: a wide step never pairs
-  if (!kSlots) return idx;
-#endif
-#ifdef N2V_ABLATE_STEP  // timing only: 2 = no pairing at all, 3 = none on rows of 4096 slots and more
-  if (N2V_ABLATE_STEP == 2 || N2V_ABLATE_STEP == 8 || (N2V_ABLATE_STEP == 3 && n >= 4096)) {
-    if (defer) h = load_hop(g.hops + vb + idx);
-    return idx;
-  }
-#endif
   // underfull / overfull by class without dividing: fl(b / avg) < 1.0 <=> b < avg
   const bool uR = K.bR < avg, uM = K.bM < avg, uO = K.bO < avg;
   const bool any_under = (nR && uR) || (nM && uM) || (nO && uO);
@@ -449,9 +353,6 @@ __device__ __forceinline__ int wedge_step(const n2v_graph &g, const UnitConsts &
   if (!any_under || !any_over) {  // the loop of :182 never runs
     if (!(r2 < p_pick)) idx = 0;
   } else {
-#ifdef N2V_BIG_STATS  // diagnostic build: pairings on rows of >= N2V_BIG_STATS slots ([2]) and the cycles / 256 they take ([3])
-    const unsigned long long big_t0 = __builtin_readcyclecounter();
-#endif
     if (!w_loaded) {  // the return position (and an empty list)
       if constexpr (kSlots) {
         sa = reinterpret_cast<const int4 *>(slot)[0];
@@ -536,14 +437,6 @@ __device__ __forceinline__ int wedge_step(const n2v_graph &g, const UnitConsts &
                                            reinterpret_cast<const uint16_t *>(g.wedge_pos) + w_off,
                                            isR, isM, lo_pick, reinterpret_cast<uint16_t *>(stage), lane);
     }
-#ifdef N2V_BIG_STATS
-    if (n >= N2V_BIG_STATS && idx >= 0) {
-#ifndef N2V_BIG_DECLINES
-      atomicAdd(status + 2, 1u);
-#endif
-      atomicAdd(status + 3, (uint32_t)((__builtin_readcyclecounter() - big_t0) >> 8));
-    }
-#endif
   }
   if (defer || idx != pick) h = load_hop(g.hops + vb + idx);
   return idx;

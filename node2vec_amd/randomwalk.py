@@ -70,7 +70,7 @@ def walk(graph: DeviceGraph, start_ids: torch.Tensor, num_walks: int, walk_lengt
          out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, check: bool = True,
          stats: Optional[dict] = None, use_edge_classes: bool = True, use_hops: bool = True,
          use_wedges: bool = True, use_wedge_kernel: bool = True, use_hops8: bool = True,
-         use_workspace: bool = False, use_wedge_slots: bool = True, use_ranked: Optional[bool] = None,
+         use_inline_rpos: bool = True, use_wedge_slots: bool = True, use_ranked: Optional[bool] = None,
          rank_ids: bool = False, use_weighted_lanes: Optional[bool] = None, use_row_sums: bool = True,
          use_rank_pairs: bool = True):
     """Launch K2.  Returns (walks int32 [n_start*num_walks, walk_length+1], valid bool).
@@ -87,11 +87,10 @@ def walk(graph: DeviceGraph, start_ids: torch.Tensor, num_walks: int, walk_lengt
     every edge by position, 8 bytes per edge + 2 per entry, skipped when it would not fit;
     use_wedges=False walks without it: same bits, searches at the steps that need the pairing).
     With all three tables the walk runs in the kernel where no step needs the wave
-    (n2v_walk_wedge.hip); use_wedge_kernel=False keeps the class-count kernel: same bits.  For
-    dyadic p, q that walk then runs in passes over a workspace lent to the library (n2v_walk_ws:
-    closed forms in the main launches, the ~1 % of steps they decline replayed out of line;
-    64 bytes per walker, allocated here); use_workspace=False keeps the one-launch kernel: same
-    bits.
+    (n2v_walk_wedge.hip); use_wedge_kernel=False keeps the class-count kernel: same bits.  The
+    hop table of that walk carries the return positions of the edges without shared neighbours in
+    its class words; use_inline_rpos=False builds it without them and the slots kernel reads them
+    from the slots: same bits.
     Exact p = q = 1 walks on unit weights need no class counts, and an entry of 8 bytes is enough for a step:
     the 8-byte hop table where the graph's field widths allow it (graph.build_hops8()), else the pair table
     (graph.build_rank_pairs(): {vertex id, degree rank} of the neighbour, rows in rank order -- any graph the
@@ -201,7 +200,7 @@ def walk(graph: DeviceGraph, start_ids: torch.Tensor, num_walks: int, walk_lengt
         # other kernel needs the plain form (the table is rebuilt in milliseconds when it changes hands)
         # (fast mode reads either form)
         want_inline = (biased and use_edge_classes and use_wedges and use_wedge_kernel
-                       and use_wedge_slots and not use_workspace and graph.wedge_slots is not None
+                       and use_wedge_slots and use_inline_rpos and graph.wedge_slots is not None
                        and (mode == "fast" or tables_regime(return_param, inout_param))
                        and graph.can_inline_rpos())
         if (graph.hops is None or (want_classes and not graph.hops_have_classes)
@@ -222,9 +221,7 @@ def walk(graph: DeviceGraph, start_ids: torch.Tensor, num_walks: int, walk_lengt
         valid = torch.empty(total, dtype=torch.uint8, device=graph.device)
     else:
         walks, valid = out
-    # include/n2v_hip.h: four words (diagnostic builds of the library count in more: N2V_DIAG_STATUS_WORDS)
-    status = torch.zeros(max(4, int(os.environ.get("N2V_DIAG_STATUS_WORDS", 4))), dtype=torch.int32,
-                         device=graph.device)
+    status = torch.zeros(4, dtype=torch.int32, device=graph.device)  # include/n2v_hip.h: four words
     g = graph.c_struct()
     if not use_edge_classes:  # the wave-per-walker kernel (what a C caller without the counts gets)
         g.edge_classes = 0
@@ -249,18 +246,10 @@ def walk(graph: DeviceGraph, start_ids: torch.Tensor, num_walks: int, walk_lengt
     if not use_row_sums:  # every row added up by the lane that needs its sum (tests: same bits)
         g.row_sums = 0
     with torch.cuda.device(graph.device):
-        ws_bytes = 0
-        if use_workspace and n_start > 0:
-            ws_bytes = int(L.n2v_walk_workspace_bytes(g, n_start, num_walks, walk_length,
-                                                      float(return_param), float(inout_param),
-                                                      MODES[mode]))
-        # (torch's caching allocator: the block is reused by the next launch on this stream)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=graph.device) if ws_bytes else None
-        rc = L.n2v_walk_ws(g, start_ids.data_ptr(), n_start, num_walks, walk_length,
-                           float(return_param), float(inout_param), seed & (2 ** 64 - 1),
-                           MODES[mode], walks.data_ptr(), valid.data_ptr(), status.data_ptr(),
-                           ws.data_ptr() if ws is not None else None, ws_bytes,
-                           _lib.current_stream_ptr())
+        rc = L.n2v_walk(g, start_ids.data_ptr(), n_start, num_walks, walk_length,
+                        float(return_param), float(inout_param), seed & (2 ** 64 - 1),
+                        MODES[mode], walks.data_ptr(), valid.data_ptr(), status.data_ptr(),
+                        _lib.current_stream_ptr())
     _lib.check(rc, "n2v_walk")
     if check:
         _lib.check_status_word(int(status[0].item()), "n2v_walk")

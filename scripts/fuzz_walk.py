@@ -106,16 +106,13 @@ while time.time() - t0 < budget:
     # unit weights, dyadic p, q: the lanes kernel (per-edge class counts) by default, the
     # wave-per-walker kernel without them -- both must match
     uec = bool(rng.random() < 0.7)
-    # the passes of n2v_walk_ws (a `make WEDGE2=1` build; the default library ignores the workspace): any
-    # number of main / resolve rounds before the finishing launch must give the same walks
-    os.environ["N2V_WEDGE2_ROUNDS"] = str(int(rng.choice([0, 1, 2, 4, 9])))
     # weighted graphs: the lane-per-walker step kernel / a wave per walker with table classes / by search
     wlanes = bool(rng.random() < 0.5)
     # (with or without the wave kernel that decides long rows by margins)
     rw.WEIGHTED_LANES_MARGINS = bool(rng.random() < 0.7)
     try:
         got, gv = rw.walk(g, starts, nw, wl, p, q, seed, use_edge_classes=uec,
-                          use_workspace=bool(rng.random() < 0.3), use_wedge_slots=bool(rng.random() < 0.7),
+                          use_inline_rpos=bool(rng.random() < 0.7), use_wedge_slots=bool(rng.random() < 0.7),
                           use_weighted_lanes=wlanes)
     except Exception:
         print("RAISED", dict(kind=kind, nv=nv, ne=len(src), weights=wk, p=p, q=q, nw=nw, wl=wl, seed=seed,

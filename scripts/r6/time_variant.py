@@ -1,5 +1,4 @@
-"""one library build (N2V_HIP_LIB), one graph, several (p, q): the exact biased walk timed (timing-only ablation
-builds of scripts/r4/build_wedge_variants.sh give different walks -- nothing is compared).
+"""one library build (N2V_HIP_LIB), one graph, several (p, q): the exact biased walk timed (nothing is compared).
   GRAPH=cfg4|cfg3 TRIM=100000 PQ="0.5,2;3,0.7;4,0.25" REPS=4 python scripts/r6/time_variant.py <label>"""
 import os, sys, time, torch
 ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -22,8 +21,7 @@ for pq in os.environ.get("PQ", "0.5,2.0;3,0.7;4,0.25").split(";"):
 
     def run(k):
         rw.walk(g, start[(k % nb) * b:(k % nb + 1) * b], 10, 80, P_, Q_, 42, out=(walks, valid), check=False,
-                mode=os.environ.get("MODE", "exact"),
-                use_workspace=bool(os.environ.get("USE_WS")))  # (USE_WS=1 + a `make WEDGE2=1` library: the passes of n2v_walk_ws)
+                mode=os.environ.get("MODE", "exact"))
 
     run(0); torch.cuda.synchronize()
     t0 = time.perf_counter()

@@ -201,7 +201,7 @@ def test_walks_over_a_mixed_wedge_table_equal_the_oracle(wide_from):
     for p, q in PQ_MIXED:
         want, wv = n2v_oracle.random_walk(rowptr, col, None, start.cpu().numpy(), 2, 25, p, q, 77, n_threads=8)
         assert g.slots_folded  # the slots kernel steps the wide rows through folded lists
-        for kw in ({}, {"use_wedge_slots": False}, {"use_wedge_kernel": False}, {"use_workspace": True}):
+        for kw in ({}, {"use_wedge_slots": False}, {"use_wedge_kernel": False}, {"use_inline_rpos": False}):
             got, gv = rw.walk(g, start, 2, 25, p, q, 77, **kw)
             assert g.wedge_mode == wide_from  # (the table was not rebuilt)
             assert np.array_equal(gv.cpu().numpy(), wv), (p, q, kw)
