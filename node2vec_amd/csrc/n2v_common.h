@@ -5,8 +5,6 @@
 
 #include "../../include/n2v_hip.h"
 
-#define N2V_WAVE 64
-
 #define N2V_HIP_CHECK(expr)                         \
   do {                                              \
     hipError_t _e = (expr);                         \
@@ -100,8 +98,6 @@ __device__ __forceinline__ n2v_hop load_hop(const n2v_hop *p) {
 }
 __device__ __forceinline__ int64_t hop_row(const n2v_hop &h) { return (int64_t)(h.row & N2V_HOP_ROW_MASK); }
 __device__ __forceinline__ int hop_deg(const n2v_hop &h) { return (int)(h.row >> N2V_HOP_DEG_SHIFT); }
-
-__device__ inline int lane_id() { return __lane_id(); }
 
 __device__ inline double readlane_f64(double v, int lane) {
   int lo = __double2loint(v), hi = __double2hiint(v);

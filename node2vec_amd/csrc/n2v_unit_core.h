@@ -32,6 +32,25 @@ struct UnitConsts {
   int dyadic;            // 1/p, 1/q are multiples of 2^-20: TR .. fO are valid
 };
 
+// ---- pieces of the per-lane step from the class counts (n2v_wedge_step.h, n2v_walk_unit.hip) ----------------
+// avg (:172) for dyadic p, q: the row sum is an exact integer combination of the class counts (T* = b * 2^20),
+// so the additions are exact in any order and the quotient is the reference's, bit for bit
+__device__ __forceinline__ double dyadic_avg(int n, int nR, int nM, int nO, const UnitConsts &K) {
+  const int64_t isum = (int64_t)nR * K.TR + (int64_t)nM * K.TM + (int64_t)nO * K.TO;
+  return ((double)isum * (1.0 / 1048576.0)) / (double)n;
+}
+
+// Values that are not dyadic: the reference's sum is rounded at every addition; any order of the same positive
+// addends agrees with it to (n - 1) 2^-53 relatively, so an underfull `pick` (class value b_pick) whose acceptance
+// clears that margin on both comparisons is decided from the counts alone: true = sampling_from_alias returns
+// `pick`.  `approx`: the average the counts give (no pass over the row), either way.
+__device__ __forceinline__ bool accept_by_counts(int n, int nR, int nM, int nO, const UnitConsts &K, double b_pick,
+                                                 double r2, double &approx) {
+  approx = ((double)nR * K.bR + (double)nM * K.bM + (double)nO * K.bO) / (double)n;
+  const double eps = ((double)n + 8.0) * 4.5e-16;
+  return b_pick < approx * (1.0 - eps) && r2 < (b_pick / approx) * (1.0 - 2.0 * eps);
+}
+
 __device__ __forceinline__ int biased_exp(double x) {
   return (int)((__double_as_longlong(x) >> 52) & 0x7ff);
 }
@@ -1073,8 +1092,7 @@ __device__ __forceinline__ int lane_case_b2(int n, int pick, double r2, double v
 // slots from the top of the row down: a slot whose predecessors' deficits sum to T is paired with
 // return slot floor(T / ER) + 1, counted from the top of the run, if there is one.  An overfull
 // `pick` is the last return slot on every graph without multi-edges: mass balance, as above.
-template <typename P>
-__device__ __forceinline__ int lane_case_a3_jump(int n, int pick, double r2, const UnitConsts &K,
+__device__ __forceinline__ int lane_case_a3_jump(int n, int pick, const UnitConsts &K,
                                                  int nR, int rpos, int nM, bool pickR, bool pickM,
                                                  int lo_pick) {
   const int nO = n - nR - nM;

@@ -404,7 +404,7 @@ __device__ __forceinline__ int near_step(int n, int pick, double r2, const UnitC
   if ((nR == n || nM == n || nO == n) && n < (1 << 20)) return pick;
   const double b_pick = pick3(isR, isM, K.bR, K.bM, K.bO);
   const double approx = ((double)nR * K.bR + (double)nM * K.bM + (double)nO * K.bO) / (double)n;
-  const double eps = ((double)n + 8.0) * 4.5e-16;  // any order of the addends against the reference's
+  const double eps = ((double)n + 8.0) * 4.5e-16;  // (accept_by_counts, n2v_unit_core.h; shared, it changes the code)
   const double lo_f = 1.0 - 2.0 * eps, hi_f = 1.0 + 2.0 * eps;
   const bool decR = nR == 0 || K.bR < approx * lo_f || K.bR > approx * hi_f;
   const bool decM = nM == 0 || K.bM < approx * lo_f || K.bM > approx * hi_f;
@@ -416,7 +416,7 @@ __device__ __forceinline__ int near_step(int n, int pick, double r2, const UnitC
   const bool any_under = (nR && uR) || (nM && uM) || (nO && uO);
   const bool any_over = (nR && !uR) || (nM && !uM) || (nO && !uO);
   if (!any_under || !any_over) return -1;
-  // the stacks, as the kernels number them
+  // the stacks, as the kernels number them (restated: as a shared function it changes their code)
   int arr = 0;
   if (uO && !(nR && uR) && !(nM && uM)) arr = 1;
   else if (!uO && nO > 0 && (!nR || uR) && (!nM || uM)) arr = 2;

@@ -54,7 +54,7 @@ struct SumState {
 };
 
 __device__ __forceinline__ void account(SumState &st, WaveLds &L, const StepCtx &c, int i,
-                                        bool act, double b, int lane, int pick) {
+                                        bool act, double b, int pick) {
   const double t = b * 1048576.0;
   const bool ok = (t >= 0.0) && (t < 2147483648.0) && (t == trunc(t));
   st.exact = st.exact && (ok || !act);
@@ -111,21 +111,8 @@ __device__ __forceinline__ void verify_maybes(const StepCtx &c, WaveLds &L, int 
     if (mem && (i >> 6) < kLdsChunks)
       atomicOr(reinterpret_cast<unsigned long long *>(&L.cls[2 * (i >> 6) + 1]),
                1ull << (i & 63));
-    account(st, L, c, i, act, b, lane, pick);
+    account(st, L, c, i, act, b, pick);
   }
-}
-
-// probs0 of chunk `chunk` (w_biased / avg); from the LDS cache when it covers the chunk
-__device__ __forceinline__ double load_vals(const StepCtx &c, WaveLds &L, int chunk, int lane,
-                                            bool bq_valid, double avg, bool &valid) {
-  const int i = chunk * 64 + lane;
-  if (bq_valid && c.n - 1 - chunk * 64 < kBqCap) {  // wave-uniform: whole chunk cached
-    valid = i < c.n;
-    const int pos = c.n - 1 - i;
-    const double b = valid ? (double)L.bq[pos] * (1.0 / 1048576.0) : 0.0;
-    return b / avg;
-  }
-  return chunk_bias<true>(c, chunk, lane, L.cls, valid) / avg;
 }
 
 // The while-loop of generate_alias_tables (:182-189), replayed until alias[pick] and
@@ -385,7 +372,7 @@ __device__ __forceinline__ int exact_draw(const StepCtx &c, uint32_t u1, uint32_
         b = wt;        // :226-227 (and q == 1)
       else
         b = wt / c.q;  // :229-230
-      account(st, L, c, i, valid && !maybe, b, lane, pick);
+      account(st, L, c, i, valid && !maybe, b, pick);
       const uint64_t mm = ballot64(maybe);
       if (mm) {
         const int cnt = __popcll(mm);

@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256, 6) void walk_fast_kernel(
   // The path is not stored word by word: a 4-byte store into a 324-byte-pitch row costs a
   // 32-byte write request.  Each lane keeps the 16 words of the 64-byte sector of walks_out
   // it is filling in LDS (word k of lane t at [k][t]: conflict-free) and stores the sector
-  // whole: four aligned 16-byte stores per 16 steps.
+  // whole: four aligned 16-byte stores per 16 steps.  (Restated from n2v_walk_wedge.hip: shared, it changes this code.)
   __shared__ int32_t path_tile[16][256];
   const int tid = threadIdx.x;
   int lo = 0;  // first word of the current sector that belongs to this row

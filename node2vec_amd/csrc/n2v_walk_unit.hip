@@ -564,8 +564,7 @@ __device__ __forceinline__ int unit_draw(const UnitStep &c, const UnitConsts &K,
   const int nO = n - nR - nM;
   double avg;
   if (kDyadic) {
-    const int64_t isum = (int64_t)nR * K.TR + (int64_t)nM * K.TM + (int64_t)nO * K.TO;
-    avg = ((double)isum * (1.0 / 1048576.0)) / (double)n;
+    avg = dyadic_avg(n, nR, nM, nO, K);
   } else {
     // left to right over the classes of N(v); runs of "other" slots by rep_add
     double sum = 0.0;
@@ -1397,6 +1396,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, kLanesWaves) void walk_exact_u
             unresolved = true;  // a count that did not fit: classify the row
           } else {
             const int nR = (int)fR, nM = need_mem ? (int)fM : 0, nO = n - nR - nM;
+            // (dyadic_avg, n2v_unit_core.h, restated: as a call the compiler orders the sum otherwise)
             const int64_t isum = (int64_t)nR * K.TR + (int64_t)nM * K.TM + (int64_t)nO * K.TO;
             const double avg = ((double)isum * (1.0 / 1048576.0)) / (double)n;  // :172
             const bool isR = x == s;

@@ -19,8 +19,9 @@
 //      bit masks (rows of <= 64 slots), else the run-by-run replay over the list, else slot by slot.
 // The path is written as whole 64-byte sectors through an LDS tile (a 4-byte store into a
 // 324-byte-pitch row costs a 32-byte write request each: 12x write amplification measured on the
-// lanes kernel).  Any dyadic p, q (the row sum is then an exact integer combination of the class
-// counts); graphs without the tables keep the kernels of n2v_walk_unit.hip.
+// lanes kernel; the writer is restated in each kernel: as a shared struct it changes their code).
+// Any dyadic p, q (the row sum is then an exact integer combination of the class counts); graphs
+// without the tables keep the kernels of n2v_walk_unit.hip.
 #include "n2v_wedge_step.h"
 
 namespace n2v {
@@ -152,9 +153,7 @@ __global__ __launch_bounds__(kWedgeThreads, kWedgeWaves) void walk_exact_wedge_k
             lo_pick = wedge_lower(g.wedge_pos, w_off, nM, pick, w_wide, isM);
           double avg;  // :172
           if constexpr (kMode == 2) {
-            // the reference's sum is rounded at every addition; any order of the same positive
-            // addends agrees with it to (n - 1) 2^-53 relatively, so an underfull `pick` whose
-            // acceptance clears that margin is decided from the counts alone
+            // (accept_by_counts, n2v_unit_core.h, restated: as a call the compiler schedules this kernel otherwise)
             const double b_pick = pick3(isR, isM, K.bR, K.bM, K.bO);
             const double approx = ((double)nR * K.bR + (double)nM * K.bM + (double)nO * K.bO) / (double)n;
             const double eps = ((double)n + 8.0) * 4.5e-16;
@@ -172,7 +171,7 @@ __global__ __launch_bounds__(kWedgeThreads, kWedgeWaves) void walk_exact_wedge_k
                                              reinterpret_cast<const uint16_t *>(g.wedge_pos) + w_off);
               avg = sum / (double)n;
             }
-          } else {
+          } else {  // (dyadic_avg, n2v_unit_core.h, restated: as a call the compiler orders the sum otherwise)
             const int64_t isum = (int64_t)nR * K.TR + (int64_t)nM * K.TM + (int64_t)nO * K.TO;
             avg = ((double)isum * (1.0 / 1048576.0)) / (double)n;
           }
@@ -196,6 +195,7 @@ __global__ __launch_bounds__(kWedgeThreads, kWedgeWaves) void walk_exact_wedge_k
               const int w_rpos = (int)(wraw >> N2V_WEDGE_RPOS_SHIFT);
               // the stacks: 1 = "other" alone underfull, 2 = "other" alone overfull, 3 = return +
               // "other" underfull, 4 = return + "other" overfull, 5 = return alone overfull, 0 = else
+              // (restated at every site: as a shared function it changes the code of every kernel that steps)
               int arr = 0;
               if (uO && !(nR && uR) && !(nM && uM)) arr = 1;
               else if (!uO && nO > 0 && (!nR || uR) && (!nM || uM)) arr = 2;
@@ -333,8 +333,7 @@ void walk_exact_wedge_slots_kernel(
       n2v_hop h;
       int idx;
       if (s >= 0) {
-        idx = wedge_step<kMode, false, true>(g, K, F, u1, u2, s, vb, n, e_prev, ec_prev, h, stage, lane,
-                                             status);
+        idx = wedge_step<kMode>(g, K, F, u1, u2, s, vb, n, e_prev, ec_prev, h, stage, lane, status);
       } else {  // first step: generate_alias_tables of unit weights is the uniform draw (:320-321)
         idx = pick_index(u1, n);
         h = load_hop(g.hops + vb + idx);
@@ -437,6 +436,7 @@ __global__ __launch_bounds__(kWedgeThreads, kWedgeWaves) void partition_step_wed
           double avg;  // :172
           int near_idx = -1;
           if constexpr (kMode == 2) {
+            // (accept_by_counts, n2v_unit_core.h, restated: as a call the compiler schedules this kernel otherwise)
             const double b_pick = pick3(isR, isM, K.bR, K.bM, K.bO);
             const double approx = ((double)nR * K.bR + (double)nM * K.bM + (double)nO * K.bO) / (double)n;
             const double eps = ((double)n + 8.0) * 4.5e-16;
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(kWedgeThreads, kWedgeWaves) void partition_step_wed
               near_idx = near_step<uint32_t>(n, pick, r2a, K, nR, w_rpos, nM, list, isR, isM, lo_pick, -1);
               avg = near_idx >= 0 ? approx : lane_row_sum<uint32_t>(n, K, nR, w_rpos, nM, list) / (double)n;
             }
-          } else {
+          } else {  // (dyadic_avg, n2v_unit_core.h, restated: as a call the compiler orders the sum otherwise)
             const int64_t isum = (int64_t)nR * K.TR + (int64_t)nM * K.TM + (int64_t)nO * K.TO;
             avg = ((double)isum * (1.0 / 1048576.0)) / (double)n;
           }
@@ -464,7 +464,7 @@ __global__ __launch_bounds__(kWedgeThreads, kWedgeWaves) void partition_step_wed
             if (!any_under || !any_over) {  // the loop of :182 never runs
               if (!(r2 < p_pick)) idx = 0;
             } else {
-              int arr = 0;
+              int arr = 0;  // the stacks, as the kernel above numbers them (restated there too)
               if (uO && !(nR && uR) && !(nM && uM)) arr = 1;
               else if (!uO && nO > 0 && (!nR || uR) && (!nM || uM)) arr = 2;
               else if (kShared && uO && nR && uR && nM && !uM) arr = 3;

@@ -475,11 +475,6 @@ struct WmLds {
   uint32_t flags[64];                     // one byte per slot of a block of 256: the slot is a shared position
 };
 
-__device__ __forceinline__ int64_t readlane_i64(int64_t v, int lane) {
-  const int lo = __builtin_amdgcn_readlane((int)(uint32_t)v, lane);
-  const int hi = __builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), lane);
-  return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-}
 // one DPP step on a 64-bit value: the value of the lane selected by kCtrl (no LDS round trip)
 template <int kCtrl>
 __device__ __forceinline__ uint64_t wm_dpp_u64(uint64_t x) {

@@ -1,6 +1,7 @@
 // n2v_wedge_step.h -- one step of an exact biased walk on a unit-weight graph from the per-edge
-// tables (hop table with class counts + wedge table, include/n2v_hip.h), by one lane: shared by the
-// kernels of n2v_walk_wedge.hip (one launch, replays inline).  Reference: the table
+// tables (hop table with class counts + wedge slots, include/n2v_hip.h), by one lane.  wedge_step has
+// one caller, walk_exact_wedge_slots_kernel (n2v_walk_wedge.hip): slots only, replays inline; pair_listed
+// is shared with the other two kernels of that file.  Reference: the table
 // generate_edge_alias_tables builds at (s, v) and sampling_from_alias on it, randomwalk.py:86-99,
 // :157-232.
 #pragma once
@@ -36,7 +37,7 @@ __device__ __forceinline__ int pair_listed(int arr, int n, int pick, double r2, 
     else if (arr == 4)
       res = lane_case_b2_jump<P>(n, pick, r2, K, nR, rpos, nM, list, isR, isM, lo_pick, below);
     else if (arr == 5)
-      res = lane_case_a3_jump<P>(n, pick, r2, K, nR, rpos, nM, isR, isM, lo_pick);
+      res = lane_case_a3_jump(n, pick, K, nR, rpos, nM, isR, isM, lo_pick);
   }
   if (res >= 0) return res;
   if constexpr (kMode == 2) {
@@ -64,26 +65,6 @@ __device__ __forceinline__ int pair_listed(int arr, int n, int pick, double r2, 
   return lane_pairing_list<P>(n, pick, r2, vR, vM, vO, nR, rpos, nM, list);
 }
 
-
-// the closed-form half of pair_listed alone: the slot the draw returns, or -1 when fp64 rounding
-// decides it (a tie, a thin margin, an arrangement without a closed form) -- the caller then has
-// the step replayed (pair_listed) somewhere else.  kMode 0, 1, 3 (dyadic p, q).
-template <typename P, int kMode>
-__device__ __forceinline__ int jump_listed(int arr, int n, int pick, double r2, const UnitConsts &K,
-                                           int nR, int rpos, int nM, ListRef<P> list, bool isR,
-                                           bool isM, int lo_pick, int below = -1) {
-  static_assert(kMode != 2, "values that are not dyadic have no closed form");
-  if (arr == 1) return lane_case_a_jump<P>(n, pick, r2, K, nR, rpos, nM, list, isR, isM, lo_pick, below);
-  if (arr == 2)
-    return lane_case_b_jump<P, kMode != 0>(n, pick, r2, K, nR, rpos, nM, list, isR, isM, lo_pick, below);
-  if constexpr (kMode == 1) {
-    if (arr == 3) return lane_case_a2_jump<P>(n, pick, r2, K, nR, rpos, nM, list, isR, isM, lo_pick, below);
-    if (arr == 4) return lane_case_b2_jump<P>(n, pick, r2, K, nR, rpos, nM, list, isR, isM, lo_pick, below);
-    if (arr == 5) return lane_case_a3_jump<P>(n, pick, r2, K, nR, rpos, nM, isR, isM, lo_pick);
-  }
-  return -1;
-}
-
 // ---- per-edge wedge slots (n2v_wedge_slots_build, include/n2v_hip.h): 16 halfwords per edge ----
 // A biased step reads the return position and the shared-position list of the edge it came along.
 // Through wedge_off that is two DEPENDENT gathers (offset, then list); the slot of edge e sits at
@@ -98,91 +79,61 @@ __device__ __forceinline__ int jump_listed(int arr, int n, int pick, double r2, 
 
 // what a kernel needs of (p, q) beyond UnitConsts, computed once
 struct StepFlags {
-  bool need_mem, always_pair, merge_r, w_wide, inline_rpos, folded;
+  bool need_mem, always_pair, merge_r, inline_rpos, folded;
 };
 __device__ __forceinline__ StepFlags step_flags(const n2v_graph &g, const UnitConsts &K, double q) {
   StepFlags f;
   f.need_mem = q != 1.0;
   f.always_pair = K.bO > 1.0;  // 1/q > 1: "other" overfull, an overfull `pick` has no quick exit
   f.merge_r = K.bR == K.bO;    // p == q: the return slot IS an "other" slot (:223-230)
-  f.w_wide = g.wedge_wide == 1;  // (a mixed table, wedge_wide >= 2: by the row, in wedge_step)
   f.inline_rpos = (g.reserved2 & N2V_HOPS_INLINE_RPOS) != 0;  // (the slots kernel's hop table only)
   f.folded = (g.reserved2 & N2V_SLOTS_FOLDED) != 0;  // the edges into wide rows have folded lists and slots
   return f;
 }
 
+
 // One biased step (s >= 0) of a walker standing on v (row vb, n slots) that came along edge e_prev
 // with class counts ec_prev: the slot sampling_from_alias returns, and in `h` the hop entry of that
-// slot.  kJumpOnly: closed forms only; returns -1 when the step has to be replayed (h is then the
-// entry of `pick`).  Otherwise the replays run here (pair_listed) and the result is always >= 0.
-// kSlots: the edge's list comes from g.wedge_slots (16-bit positions only) instead of wedge_off.
-// A saturated class count (tables that do not belong to this graph) flags N2V_ST_RANGE and keeps
-// `pick`, as the one-launch kernel does.  kMode 0, 1, 3 (dyadic p, q); with kSlots also 2 (values
-// that are not dyadic: reference-order row sum, every pairing replayed).
-template <int kMode, bool kJumpOnly, bool kSlots>
+// slot.  One caller, walk_exact_wedge_slots_kernel: the edge's list comes from g.wedge_slots (16-bit
+// positions, folded for the edges into wide rows), and the replays run here, inline (pair_listed), so the
+// result is always >= 0.  A saturated class count (tables that do not belong to this graph) flags
+// N2V_ST_RANGE and keeps `pick`, as the one-launch kernel does.  kMode 0, 1, 3: dyadic p, q, by the
+// arrangements compiled in (pair_listed); 2: values that are not dyadic -- reference-order row sum, every
+// pairing replayed.
+template <int kMode>
 __device__ __forceinline__ int wedge_step(const n2v_graph &g, const UnitConsts &K, const StepFlags &F,
                                           uint32_t u1, uint32_t u2, int32_t s, int64_t vb, int n,
                                           int64_t e_prev, uint32_t ec_prev, n2v_hop &h,
-                                          uint32_t *stage, int lane, uint32_t *status,
-                                          uint16_t *lds_list = nullptr);
-
-// the step of a walker standing on a WIDE row of a mixed wedge table (out of line it was measured no faster):
-// it is taken by a few per cent of the steps at most, and inlined into the slots kernel its 32-bit
-// instances of the closed forms cost every step registers (scratch 24 -> 40 B per lane in <0>, 100 -> 144 in <1>)
-template <int kMode, bool kJumpOnly>
-__device__ __forceinline__ int
-wedge_step_wide(const n2v_graph &g, const UnitConsts &K, const StepFlags &F, uint32_t u1, uint32_t u2, int32_t s,
-                int64_t vb, int n, int64_t e_prev, uint32_t ec_prev, n2v_hop &h, uint32_t *stage, int lane,
-                uint32_t *status) {
-  StepFlags Fw = F;
-  Fw.w_wide = true;
-  return wedge_step<kMode, kJumpOnly, false>(g, K, Fw, u1, u2, s, vb, n, e_prev, ec_prev, h, stage, lane, status,
-                                             nullptr);
-}
-
-template <int kMode, bool kJumpOnly, bool kSlots>
-__device__ __forceinline__ int wedge_step(const n2v_graph &g, const UnitConsts &K, const StepFlags &F,
-                                          uint32_t u1, uint32_t u2, int32_t s, int64_t vb, int n,
-                                          int64_t e_prev, uint32_t ec_prev, n2v_hop &h,
-                                          uint32_t *stage, int lane, uint32_t *status,
-                                          uint16_t *lds_list) {
+                                          uint32_t *stage, int lane, uint32_t *status) {
   constexpr bool kShared = kMode == 1 || kMode == 2;
   bool folded = false;  // this lane stands on a wide row and reads a folded slot / list
-  if constexpr (kSlots) {
-    // mixed wedge table (g.wedge_wide = T >= 2): the edges into a row of T entries or more have
-    // uint32 lists and no slot -- the step of a walker standing on such a row goes through wedge_off
-    // (a per-lane branch: the other lanes of the wave keep their slots)
-    if (g.wedge_wide >= 2 && n >= g.wedge_wide) {
-      // (round 6) a wide row: its edges have FOLDED lists and slots (ListRef, n2v_wedge_slots_fold) and it takes the
-      // step below like every other row.  (The launcher gives a mixed table without folded slots to the kernel that
-      // reads wedge_off; rounds 4 - 5 stepped such a row here through a second, 32-bit instance of this function,
-      // wedge_step_wide: every wave with one lane on a wide row executed both.)
-      if (!(F.folded && n - g.wedge_wide <= 65536)) {  // slots that do not belong to this graph
-        atomicOr(status, N2V_ST_RANGE);
-        const int pk = pick_index(u1, n);
-        h = load_hop(g.hops + vb + pk);
-        return pk;
-      }
-      folded = true;
+  // mixed wedge table (g.wedge_wide = T >= 2): a row of T entries or more is a WIDE row.  Its edges have
+  // FOLDED lists and slots (ListRef, n2v_wedge_slots_fold) and it takes the step below like every other row
+  // (a per-lane flag: the other lanes of the wave keep their plain slots).  The launcher gives a mixed
+  // table without folded slots to the kernel that reads wedge_off.
+  if (g.wedge_wide >= 2 && n >= g.wedge_wide) {
+    if (!(F.folded && n - g.wedge_wide <= 65536)) {  // slots that do not belong to this graph
+      atomicOr(status, N2V_ST_RANGE);
+      const int pk = pick_index(u1, n);
+      h = load_hop(g.hops + vb + pk);
+      return pk;
     }
+    folded = true;
   }
   const int pick = pick_index(u1, n);
   int idx = pick;
-  const bool w_wide = F.w_wide || wedge_row_wide(g.wedge_wide, n);  // width of this step's list (!kSlots)
   // an edge without shared neighbours may carry its return position in the class word itself
-  // (N2V_EC_INLINE, slots kernel only): its slot is then never fetched
-  const bool inl = kSlots && F.inline_rpos && ec_prev != 0xffffffffu && (ec_prev & N2V_EC_INLINE) != 0u;
+  // (N2V_EC_INLINE): its slot is then never fetched
+  const bool inl = F.inline_rpos && ec_prev != 0xffffffffu && (ec_prev & N2V_EC_INLINE) != 0u;
   const uint32_t fR = inl ? ((ec_prev >> N2V_EC_RETURN_SHIFT) & 0x7fu) : (ec_prev >> N2V_EC_RETURN_SHIFT);
   const uint32_t fM = inl ? 0u : (ec_prev & N2V_EC_SHARED_MASK);
   const bool counts_ok = inl || (fR != N2V_EC_RETURN_SAT && fM != N2V_EC_SHARED_MASK);
-  // this step's wedge list: its offset (its slot) is requested before the hop so both loads
+  // this step's wedge list: its slot is requested before the hop so both loads
   // overlap; steps whose edge has no shared neighbour need it only if the pairing runs (lazy)
-  uint64_t wraw = 0;
   int4 sa = make_int4(0, 0, 0, 0), sb = make_int4(0, 0, 0, 0);
   bool w_loaded = inl;
   if (inl) sa.x = (int)(ec_prev & 0xffffu);  // halfword 0: the return position (16-bit positions), 1: below = 0
-  const uint16_t *slot = nullptr;
-  if constexpr (kSlots) slot = reinterpret_cast<const uint16_t *>(g.wedge_slots) + e_prev * 16;
+  const uint16_t *slot = reinterpret_cast<const uint16_t *>(g.wedge_slots) + e_prev * 16;
   // what the slot says once its first 16 bytes are in `sa`.  A FOLDED slot (n2v_wedge_slots_fold: the edge leads into
   // a wide row) packs three more numbers: whether the return position lies in the upper part, the entries of the list
   // in the lower part (ListRef::nlow), and the high bits of counts that a list of up to 2^20 entries needs --
@@ -208,14 +159,10 @@ __device__ __forceinline__ int wedge_step(const n2v_graph &g, const UnitConsts &
   // closed forms with margins, else for the row sum --: fetched there if not here)
   if (!inl && counts_ok &&
       ((F.need_mem && fM > 0) || (F.always_pair && (fM > 0 || fR > 0)))) {
-    if constexpr (kSlots) {
-      // (asking for the second half only when the list has more than six entries was measured
-      // and changes nothing: -3 .. +4 % by (p, q), profiles/r4i_time_slots_on_demand.log)
-      sa = reinterpret_cast<const int4 *>(slot)[0];
-      sb = reinterpret_cast<const int4 *>(slot)[1];
-    } else {
-      wraw = g.wedge_off[e_prev];
-    }
+    // (asking for the second half only when the list has more than six entries was measured
+    // and changes nothing: -3 .. +4 % by (p, q), profiles/r4i_time_slots_on_demand.log)
+    sa = reinterpret_cast<const int4 *>(slot)[0];
+    sb = reinterpret_cast<const int4 *>(slot)[1];
     w_loaded = true;
   }
   // An edge whose class word carries its return position (`inl`: no shared neighbours) has everything the decision
@@ -230,116 +177,64 @@ __device__ __forceinline__ int wedge_step(const n2v_graph &g, const UnitConsts &
   // (A list that is not inside the slot is searched in memory, a chain of dependent probes: there the entry of `pick`
   // is requested at once, as before, and arrives behind them -- waiting with it cost the graph trimmed at the
   // reference's cap, whose hub steps are such searches, 10 %: 14.0 -> 12.6 G.)
-  const bool defer = inl || (kSlots && w_loaded && fM <= (uint32_t)kSlotShort);
+  const bool defer = inl || (w_loaded && fM <= (uint32_t)kSlotShort);
   if (!defer) h = load_hop(g.hops + vb + pick);
   if (!counts_ok) {
     atomicOr(status, N2V_ST_RANGE);
     return idx;
   }
   const int nR = F.merge_r ? 0 : (int)fR, nM = F.need_mem ? (int)fM : 0, nO = n - nR - nM;
-  int64_t w_off = (int64_t)(wraw & N2V_WEDGE_OFF_MASK);
   // (rows are sorted by neighbour: the slots that lead back to s are one run)
   const int rp0 = slot_rpos();
   const bool isR = defer ? (nR > 0 && pick >= rp0 && pick < rp0 + nR) : (!F.merge_r && h.col == s);
   bool isM = false;
   int lo_pick = 0;  // entries of the edge's list below `pick`
-  if (F.need_mem && !isR && nM > 0) {  // :226
-    if constexpr (kSlots)
-      lo_pick = slot_lower(sa, sb, nM, pick, reinterpret_cast<const uint16_t *>(g.wedge_pos), isM, slot_nlow(),
-                           g.wedge_wide);
-    else
-      lo_pick = wedge_lower(g.wedge_pos, w_off, nM, pick, w_wide, isM);
-  }
+  if (F.need_mem && !isR && nM > 0)  // :226
+    lo_pick = slot_lower(sa, sb, nM, pick, reinterpret_cast<const uint16_t *>(g.wedge_pos), isM, slot_nlow(),
+                         g.wedge_wide);
   const double r2 = (double)u2 * (1.0 / 4294967296.0);
   double avg;  // :172
   if constexpr (kMode == 2) {
-    static_assert(!kJumpOnly, "values that are not dyadic: replays inline");
-    // the reference's sum is rounded at every addition; any order of the same positive addends
-    // agrees with it to (n - 1) 2^-53 relatively, so an underfull `pick` whose acceptance clears
-    // that margin is decided from the counts alone; otherwise the row is added up in the
-    // reference's order, run by run (lane_row_sum), the short list read from this lane's LDS row
-    const double b_pick = pick3(isR, isM, K.bR, K.bM, K.bO);
-    const double approx = ((double)nR * K.bR + (double)nM * K.bM + (double)nO * K.bO) / (double)n;
-    const double eps = ((double)n + 8.0) * 4.5e-16;
-    if (b_pick < approx * (1.0 - eps) && r2 < (b_pick / approx) * (1.0 - 2.0 * eps)) {
+    // decided from the counts alone, or else the row is added up in the reference's order, run by run (lane_row_sum)
+    double approx;
+    if (accept_by_counts(n, nR, nM, nO, K, pick3(isR, isM, K.bR, K.bM, K.bO), r2, approx)) {
       avg = approx;  // only the (decided) comparison below reads it
     } else {
       // (round 4) Before the row is added up in the reference's order: the closed forms on the values
       // the COUNTS give, with margins (near_step, n2v_unit_near.h).  Anything closer than the margin
       // goes on to the exact row sum and the replays below.
-      if constexpr (kSlots) {
-        if (!w_loaded) {  // an edge without shared neighbours whose step got here: its return position
-          sa = reinterpret_cast<const int4 *>(slot)[0];
-          sb = reinterpret_cast<const int4 *>(slot)[1];
-          w_loaded = true;
-        }
-        {
-          const uint16_t *nlist = slot + 2;
-          if (nM > kSlotShort)
-            nlist = reinterpret_cast<const uint16_t *>(g.wedge_pos) +
-                    ((uint64_t)(uint32_t)sa.z | ((uint64_t)(uint32_t)sa.w << 32));
-          const int res = near_step<uint16_t>(n, pick, r2, K, nR, slot_rpos(), nM,
-                                              ListRef<uint16_t>(nlist, slot_nlow(), g.wedge_wide), isR, isM, lo_pick,
-                                              slot_below());
-          if (res >= 0) {
-            if (defer || res != pick) h = load_hop(g.hops + vb + res);
-            return res;
-          }
-        }
-        if (g.row_sums != nullptr && n >= g.row_sums_from) {
-          // a long row: the sum of this edge's table was added up once (n2v_edge_row_sums_build: this routine, these bits)
-          avg = g.row_sums[e_prev] / (double)n;
-        } else {
-        const uint16_t *sum_list = slot + 2;
-        if (nM > kSlotShort) {
-          sum_list = reinterpret_cast<const uint16_t *>(g.wedge_pos) +
-                     ((uint64_t)(uint32_t)sa.z | ((uint64_t)(uint32_t)sa.w << 32));
-        } else if (lds_list != nullptr) {
-          uint32_t *row = reinterpret_cast<uint32_t *>(lds_list);
-          row[0] = (uint32_t)sa.y;
-          row[1] = (uint32_t)sa.z;
-          row[2] = (uint32_t)sa.w;
-          row[3] = (uint32_t)sb.x;
-          row[4] = (uint32_t)sb.y;
-          row[5] = (uint32_t)sb.z;
-          row[6] = (uint32_t)sb.w;
-          sum_list = lds_list;
-        }
-        avg = lane_row_sum<uint16_t>(n, K, nR, slot_rpos(), nM, ListRef<uint16_t>(sum_list, slot_nlow(), g.wedge_wide)) /
-              (double)n;
-        }
-      } else {
-        // through wedge_off (the wide rows of a mixed table): the same two stages on the list in memory
-        if (!w_loaded) {
-          wraw = g.wedge_off[e_prev];
-          w_off = (int64_t)(wraw & N2V_WEDGE_OFF_MASK);
-          w_loaded = true;
-        }
-        const int rp = (int)(wraw >> N2V_WEDGE_RPOS_SHIFT);
-        int res = -1;
-        if (w_wide)
-          res = near_step<uint32_t>(n, pick, r2, K, nR, rp, nM,
-                                    reinterpret_cast<const uint32_t *>(g.wedge_pos) + w_off, isR, isM, lo_pick, -1);
-        else
-          res = near_step<uint16_t>(n, pick, r2, K, nR, rp, nM,
-                                    reinterpret_cast<const uint16_t *>(g.wedge_pos) + w_off, isR, isM, lo_pick, -1);
+      if (!w_loaded) {  // an edge without shared neighbours whose step got here: its return position
+        sa = reinterpret_cast<const int4 *>(slot)[0];
+        sb = reinterpret_cast<const int4 *>(slot)[1];
+        w_loaded = true;
+      }
+      {
+        const uint16_t *nlist = slot + 2;
+        if (nM > kSlotShort)
+          nlist = reinterpret_cast<const uint16_t *>(g.wedge_pos) +
+                  ((uint64_t)(uint32_t)sa.z | ((uint64_t)(uint32_t)sa.w << 32));
+        const int res = near_step<uint16_t>(n, pick, r2, K, nR, slot_rpos(), nM,
+                                            ListRef<uint16_t>(nlist, slot_nlow(), g.wedge_wide), isR, isM, lo_pick,
+                                            slot_below());
         if (res >= 0) {
-          if (res != pick) h = load_hop(g.hops + vb + res);
+          if (defer || res != pick) h = load_hop(g.hops + vb + res);
           return res;
         }
-        double sum;
-        if (g.row_sums != nullptr && n >= g.row_sums_from)
-          sum = g.row_sums[e_prev];
-        else if (w_wide)
-          sum = lane_row_sum<uint32_t>(n, K, nR, rp, nM, reinterpret_cast<const uint32_t *>(g.wedge_pos) + w_off);
-        else
-          sum = lane_row_sum<uint16_t>(n, K, nR, rp, nM, reinterpret_cast<const uint16_t *>(g.wedge_pos) + w_off);
-        avg = sum / (double)n;
+      }
+      if (g.row_sums != nullptr && n >= g.row_sums_from) {
+        // a long row: the sum of this edge's table was added up once (n2v_edge_row_sums_build: this routine, these bits)
+        avg = g.row_sums[e_prev] / (double)n;
+      } else {
+        const uint16_t *sum_list = slot + 2;
+        if (nM > kSlotShort)
+          sum_list = reinterpret_cast<const uint16_t *>(g.wedge_pos) +
+                     ((uint64_t)(uint32_t)sa.z | ((uint64_t)(uint32_t)sa.w << 32));
+        avg = lane_row_sum<uint16_t>(n, K, nR, slot_rpos(), nM, ListRef<uint16_t>(sum_list, slot_nlow(), g.wedge_wide)) /
+              (double)n;
       }
     }
   } else {
-    const int64_t isum = (int64_t)nR * K.TR + (int64_t)nM * K.TM + (int64_t)nO * K.TO;
-    avg = ((double)isum * (1.0 / 1048576.0)) / (double)n;
+    avg = dyadic_avg(n, nR, nM, nO, K);
   }
   const double p_pick = pick3(isR, isM, K.bR, K.bM, K.bO) / avg;  // :173
   if (p_pick < 1.0 && r2 < p_pick) {  // an accepted underfull slot is final
@@ -353,90 +248,28 @@ __device__ __forceinline__ int wedge_step(const n2v_graph &g, const UnitConsts &
   if (!any_under || !any_over) {  // the loop of :182 never runs
     if (!(r2 < p_pick)) idx = 0;
   } else {
-    if (!w_loaded) {  // the return position (and an empty list)
-      if constexpr (kSlots) {
-        sa = reinterpret_cast<const int4 *>(slot)[0];
-      } else {
-        wraw = g.wedge_off[e_prev];
-        w_off = (int64_t)(wraw & N2V_WEDGE_OFF_MASK);
-      }
-    }
-    int w_rpos;
-    if constexpr (kSlots)
-      w_rpos = slot_rpos();
-    else
-      w_rpos = (int)(wraw >> N2V_WEDGE_RPOS_SHIFT);
+    if (!w_loaded) sa = reinterpret_cast<const int4 *>(slot)[0];  // the return position (and an empty list)
+    const int w_rpos = slot_rpos();
     // the stacks: 1 = "other" alone underfull, 2 = "other" alone overfull, 3 = return + "other"
     // underfull, 4 = return + "other" overfull, 5 = return alone overfull, 0 = else
+    // (restated at every site: as a shared function it changes the code of every kernel that steps)
     int arr = 0;
     if (uO && !(nR && uR) && !(nM && uM)) arr = 1;
     else if (!uO && nO > 0 && (!nR || uR) && (!nM || uM)) arr = 2;
     else if (kShared && uO && nR && uR && nM && !uM) arr = 3;
     else if (kShared && !uO && nO > 0 && nR && !uR && nM && uM) arr = 4;
     else if (kShared && uO && nR && !uR && nM && uM) arr = 5;
-    if constexpr (kSlots) {
-      // entries of the list below the return position (stored: saves the routines a search)
-      const int w_below = slot_below();
-      // the list as the pairing routines read it: inside the slot, or in wedge_pos
-      const uint16_t *list_p = slot + 2;
-      if (nM > kSlotShort)
-        list_p = reinterpret_cast<const uint16_t *>(g.wedge_pos) +
-                 ((uint64_t)(uint32_t)sa.z | ((uint64_t)(uint32_t)sa.w << 32));
-      const ListRef<uint16_t> list(list_p, slot_nlow(), g.wedge_wide);
-      if constexpr (kJumpOnly) {
-        idx = jump_listed<uint16_t, kMode>(arr, n, pick, r2, K, nR, w_rpos, nM, list, isR, isM, lo_pick,
-                                           w_below);
-        if (idx < 0) {
-          if (defer) h = load_hop(g.hops + vb + pick);
-          return -1;
-        }
-      } else {
-        bool done = false;
-        if (kMode != 2 && lds_list != nullptr && nM <= kSlotShort) {
-          // (optional, measured and NOT used by the kernels: a short list copied from the slot's
-          // registers to 32 bytes of LDS per lane for the closed forms to read -- 20.3 against
-          // 23.2 G steps/s at (0.5, 2), 16.4 against 18.6 G at (4, 0.25): the flat loads and the
-          // LDS it takes (5 waves per SIMD instead of 6) cost more than probes of a sector that
-          // is still cached, profiles/r4k_time_lds_list_cfg4.log)
-          uint32_t *row = reinterpret_cast<uint32_t *>(lds_list);
-          row[0] = (uint32_t)sa.y;
-          row[1] = (uint32_t)sa.z;
-          row[2] = (uint32_t)sa.w;
-          row[3] = (uint32_t)sb.x;
-          row[4] = (uint32_t)sb.y;
-          row[5] = (uint32_t)sb.z;
-          row[6] = (uint32_t)sb.w;
-          if constexpr (kMode != 2)
-            idx = jump_listed<uint16_t, kMode>(arr, n, pick, r2, K, nR, w_rpos, nM,
-                                               ListRef<uint16_t>(lds_list, slot_nlow(), g.wedge_wide), isR, isM,
-                                               lo_pick, w_below);
-          done = idx >= 0;
-        }
-        if (!done)  // long lists; a tie or a thin margin: the replays read the list in memory
-          idx = pair_listed<uint16_t, kMode>(arr, n, pick, r2, K, avg, nR, w_rpos, nM, list, isR, isM,
-                                             lo_pick, reinterpret_cast<uint16_t *>(stage), lane, w_below);
-      }
-    } else if constexpr (kJumpOnly) {
-      // a plain branch on the (uniform) list width: never a select between two loads
-      if (w_wide)
-        idx = jump_listed<uint32_t, kMode>(arr, n, pick, r2, K, nR, w_rpos, nM,
-                                           reinterpret_cast<const uint32_t *>(g.wedge_pos) + w_off,
-                                           isR, isM, lo_pick);
-      else
-        idx = jump_listed<uint16_t, kMode>(arr, n, pick, r2, K, nR, w_rpos, nM,
-                                           reinterpret_cast<const uint16_t *>(g.wedge_pos) + w_off,
-                                           isR, isM, lo_pick);
-      if (idx < 0) return -1;
-    } else {
-      if (w_wide)
-        idx = pair_listed<uint32_t, kMode>(arr, n, pick, r2, K, avg, nR, w_rpos, nM,
-                                           reinterpret_cast<const uint32_t *>(g.wedge_pos) + w_off,
-                                           isR, isM, lo_pick, stage, lane);
-      else
-        idx = pair_listed<uint16_t, kMode>(arr, n, pick, r2, K, avg, nR, w_rpos, nM,
-                                           reinterpret_cast<const uint16_t *>(g.wedge_pos) + w_off,
-                                           isR, isM, lo_pick, reinterpret_cast<uint16_t *>(stage), lane);
-    }
+    // entries of the list below the return position (stored: saves the routines a search)
+    const int w_below = slot_below();
+    // the list as the pairing routines read it: inside the slot, or in wedge_pos
+    const uint16_t *list_p = slot + 2;
+    if (nM > kSlotShort)
+      list_p = reinterpret_cast<const uint16_t *>(g.wedge_pos) +
+               ((uint64_t)(uint32_t)sa.z | ((uint64_t)(uint32_t)sa.w << 32));
+    const ListRef<uint16_t> list(list_p, slot_nlow(), g.wedge_wide);
+    // (a tie or a thin margin: the replays read the list in memory)
+    idx = pair_listed<uint16_t, kMode>(arr, n, pick, r2, K, avg, nR, w_rpos, nM, list, isR, isM,
+                                       lo_pick, reinterpret_cast<uint16_t *>(stage), lane, w_below);
   }
   if (defer || idx != pick) h = load_hop(g.hops + vb + idx);
   return idx;

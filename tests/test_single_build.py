@@ -28,5 +28,10 @@ def test_no_environment_lookups():
     assert [where for p in SOURCES for where, line in _lines(p) if "getenv" in line] == []
 
 
+def test_dead_forms_of_the_wedge_step_are_gone():
+    gone = re.compile(r"\b(kJumpOnly|wedge_step_wide|jump_listed|lds_list)\b")
+    assert [where for p in SOURCES for where, line in _lines(p) if gone.search(line)] == []
+
+
 def test_workspace_pass_variant_is_gone():
     assert not os.path.exists(os.path.join(CSRC, "n2v_walk_wedge2.hip"))
