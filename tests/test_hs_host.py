@@ -338,3 +338,88 @@ def test_node2vecspark_host_logic():
         n2v.embedding()
     with pytest.raises(ValueError):
         n2v.get_vector(1)
+
+
+# ---- codes of 33 .. 64 bits (tests/hs_deep_cases.py) ---------------------------------------------------------
+
+@pytest.mark.parametrize("V,longest", [(33, 32), (34, 33), (64, 63), (65, 64)])
+def test_tree_build_at_the_depth_boundary(lib, V, longest):
+    """Fibonacci counts: a chain whose two deepest words have codes of `longest` bits; 65 bits are refused"""
+    import hs_deep_cases as deep
+
+    t = _check_tree(deep.fib_counts(V))  # word for word against create_binary_tree, codes and points
+    assert int(t.lengths.max()) == longest and int((t.lengths == longest).sum()) == 2
+    assert t.codes.dtype == np.uint64 and t.path_off.dtype == np.int64
+    if V == 65:
+        assert any((int(c) >> 63) & 1 for c in t.codes)  # as a Python int: no sign, no wrap
+
+
+def test_tree_build_refuses_a_code_of_65_bits(lib):
+    import hs_deep_cases as deep
+    from node2vec_amd import hs
+
+    assert int(deep.fib_counts(66).sum()) < 2 ** 61  # refused for its depth, not for its sums
+    with pytest.raises(ValueError):
+        hs.build_tree(deep.fib_counts(66))
+
+
+def test_mixed_counts_give_short_and_long_codes(lib):
+    import hs_deep_cases as deep
+
+    c = deep.mixed_counts()
+    assert len(c) == 80 and (np.diff(c) <= 0).all()
+    t = _check_tree(c)
+    assert int(t.lengths.min()) == 2 and int(t.lengths.max()) == 48
+    assert int((t.lengths <= 8).sum()) >= 30 and int((t.lengths > 32).sum()) >= 10
+
+
+def test_model_keeps_bit_63_of_the_codes(lib):
+    """uint64 -> int64 -> torch in HsModel: the tensor, viewed back as uint64, is tree.codes"""
+    import hs_deep_cases as deep
+    from node2vec_amd import hs
+
+    m = hs.HsModel(deep.vocab(deep.fib_counts(65)), 16, 5, seed=1)
+    assert m.codes.dtype == torch.int64 and int(m.codes.min()) < 0  # bit 63 is the sign there
+    back = m.codes.cpu().numpy().view(np.uint64)
+    assert np.array_equal(back, m.tree.codes) and any((int(c) >> 63) & 1 for c in back)
+    assert np.array_equal(m.path_off.cpu().numpy(), m.tree.path_off)
+    assert np.array_equal(m.points.cpu().numpy(), m.tree.points)
+
+
+def _deep_mutants(tree, V):
+    """trees that are wrong only past bit / level 31 (V = 65: also only at bit / level 63)"""
+    import hs_deep_cases as deep
+
+    out = {"codes masked to 32 bits": (tree.path_off, tree.points, tree.codes & np.uint64(0xFFFFFFFF)),
+           "paths cut to 32 nodes": deep.cut_paths(tree, 32)}
+    if V == 65:
+        out["bit 63 cleared"] = (tree.path_off, tree.points, tree.codes & np.uint64(2 ** 63 - 1))
+        out["paths cut to 63 nodes"] = deep.cut_paths(tree, 63)
+    return out
+
+
+@pytest.mark.parametrize("V", [34, 65])
+def test_deep_cases_tell_a_wrong_deep_level_from_the_true_tree(lib, hs_cpu, V):
+    """A condition on the INPUTS of tests/test_hs_deep_gpu.py, shown with the restatement alone: the
+    corpus trains bit 32 (V = 65: and bit 63) of a code and level 32 (63) of a path, so a trainer that
+    gets them wrong cannot produce the restatement's bits."""
+    import hs_deep_cases as deep
+    from node2vec_amd import hs
+
+    dim = 16
+    tree = hs.build_tree(deep.fib_counts(V))
+    walks = deep.corpus(V, seed=V)
+
+    def train(path_off, points, codes):
+        s0, s1 = deep.syn0_init(V, dim, seed=V), np.zeros((V - 1, dim), np.float32)
+        n = deep.cpu_train(hs_cpu, walks, s0, s1, path_off, points, codes, seed=7, window=deep.WINDOW)
+        return s0, s1, n
+
+    t0, t1, n = train(tree.path_off, tree.points, tree.codes)
+    assert n > 0 and np.abs(t1).max() > 1e-3
+    for name, (off, pts, codes) in _deep_mutants(tree, V).items():
+        assert len(off) == V + 1 and off[-1] == len(pts) <= len(tree.points)
+        m0, m1, mn = train(off, pts, codes)
+        assert mn == n, name  # the pairs do not depend on the tree
+        changed = not (np.array_equal(m0, t0) and np.array_equal(m1, t1))
+        assert changed, f"{name}: the case does not notice"
