@@ -3,8 +3,11 @@
 Both word2vec updates skip a node or target whose f <= -6 or f >= 6 BEFORE any store.  So a launch of
 many unsynchronised waves computes exactly what one thread computes when
   * no two sentences train the same row, and
-  * the rows every sentence must read (HS: the top of the tree; SGNS: the negative samples) are
-    saturated, so nobody ever writes them.
+  * the rows every sentence must read (HS: the top of the tree; SGNS and CBOW: the negative samples)
+    are saturated, so nobody ever writes them.
+CBOW: every target of a position other than its centre word is the sink, whose f against the summed
+(or averaged) context is >= 6; what trains is syn1neg[centre] and syn0[context], all of them words of
+one sentence.
 `prove` checks those conditions under the CPU restatement alone; only then is a GPU comparison with
 the restatement's joint run meaningful (tests/test_train_geometry_cpu.py, test_train_geometry_gpu.py).
 
@@ -177,3 +180,33 @@ def sgns_case(oracle, dim, sentences=32, oov=False, saturated=SATURATED):
         return oracle.sgns_train(w, s0, s1, cum, None, exp, n_vocab, base, SEED, dim, WINDOW, NEGATIVE, alpha)
 
     return Case(f"sgns-{dim}-{sentences}-{int(oov)}", dim, walks, m0, m1, [SINK], run)
+
+
+# ---- CBOW with negative sampling -----------------------------------------------------------------------------
+
+def cbow_case(cbow_cpu, dim, sentences=32, oov=False, cbow_mean=1, saturated=SATURATED, negative=NEGATIVE):
+    """the corpus of sgns_case under the CBOW update: every draw of a position is the sink word 0, whose
+    syn1neg row [saturated, 0, ...] has f = saturated * neu1[0] >= 6 -- neu1[0] is the sum (cbow_mean 0)
+    or the mean (1) of syn0[context, 0], all 1 at the start, and only raised: the label-1 update adds
+    g * neu1 with g > 0 to syn1neg[centre], so work[0] = g * syn1neg[centre, 0] >= 0.  What trains is
+    syn1neg[centre] and syn0[context], words of the same sentence.  CBOW has no window cache: rows go
+    back by plain stores, so syn0 takes word2vec's own initialisation.  Any `negative` does: every
+    draw is the sink."""
+    from test_cbow_host import cpu_train
+
+    n_vocab = V_WORDS + 1
+    rng = np.random.default_rng(3000 * dim + 10 * sentences + int(oov))
+    words = 1 + rng.permutation(V_WORDS)
+    groups = np.split(words, sentences)
+    m0 = _syn0(rng, n_vocab, dim)
+    m1 = np.zeros((n_vocab, dim), np.float32)
+    m1[SINK, 0] = saturated
+    walks = _sentences(rng, groups, oov)
+    assert not (walks == SINK).any()
+    cum = sgns_cum_table()
+
+    def run(w, s0, s1, base, alpha):
+        return int(cpu_train(cbow_cpu, w, s0, s1, cum, None, n_vocab, base, SEED, dim, WINDOW, negative, alpha,
+                             cbow_mean))
+
+    return Case(f"cbow-{dim}-{sentences}-{int(oov)}-{cbow_mean}-k{negative}", dim, walks, m0, m1, [SINK], run)

@@ -6,6 +6,11 @@ every VEC instance of the kernel, at a dimension that fills the wave and at one 
 cbow_mean 0 and 1.  Every bit case asserts from the restatement alone that it trains, that a window
 holds a word twice and that a negative draw equals its centre word.  The statistical tests bound the
 hogwild mode's quality.
+
+Elsewhere: test_cbow_groups_gpu.py puts `negative` on the edges of the kernel's target groups for every
+VEC, the batches of draws at their extremes and long windows over the context groups (every bit case
+here has negative = 5); test_train_geometry_gpu.py compares the hogwild launch on many waves bit for
+bit on the conflict-free corpora of conflict_free.py.
 """
 import numpy as np
 import pandas as pd

@@ -1,7 +1,8 @@
 """CBOW with negative sampling (sg=0), the parts that need no GPU: the CPU restatement
 tests/cpu_cbow/n2v_cbow_cpu.c against a second restatement in numpy float64 with ordinary dot
 products, hand-made sentences whose result can be written down, the constructor contract of
-Node2VecHIP / SgnsModel, and the argument checks of n2v_cbow_train."""
+Node2VecHIP / SgnsModel, the argument checks of n2v_cbow_train, and the integer replay
+tests/cbow_groups.py (which rows a position touches) against the restatement's own counters."""
 import ctypes as C
 import os
 import subprocess
@@ -144,6 +145,52 @@ def test_c_restatement_matches_independent_float64_restatement(cbow_cpu, cbow_me
         np.testing.assert_allclose(c0, r0, rtol=2e-4, atol=2e-6)
         np.testing.assert_allclose(c1, r1, rtol=2e-4, atol=2e-6)
         assert np.abs(c0 - s0).max() > 1e-4  # and the pass did change the vectors
+
+
+def bit_corpus(n_tok, rows, ln, seed, sample, min_count=1):
+    """the Zipf corpus of test_sgns_gpu._setup without a GPU: (idx, cum_table, sample_int or None) as
+    int32 / uint32 / uint32 numpy arrays, what SgnsModel derives from the same walks"""
+    from node2vec_amd import sgns
+
+    gen = torch.Generator().manual_seed(seed)
+    p = 1.0 / torch.arange(1, n_tok + 1, dtype=torch.float64)
+    walks = torch.multinomial(p, rows * ln, replacement=True, generator=gen).reshape(rows, ln).to(torch.int32)
+    vocab = sgns.build_vocab(walks, min_count)
+    idx = vocab.index_of[walks.long()].numpy()
+    cum = sgns.make_cum_table(vocab.counts).numpy().view(np.uint32)
+    si = sgns.make_sample_int(vocab.counts, sample)
+    return idx, cum, None if si is None else si.numpy().view(np.uint32)
+
+
+@pytest.mark.parametrize("sample", [0.0, 1e-2])
+@pytest.mark.parametrize("window,negative", [(5, 5), (1, 1), (32, 21), (5, 32)])
+def test_replay_of_touched_rows_matches_the_restatements_counters(cbow_cpu, window, negative, sample):
+    """tests/cbow_groups.py on the corpus of the bit tests (12 rows of 21 tokens, two launches): its
+    trained positions, its draws equal to their centre and its windows that hold a word twice are the
+    restatement's return value, stats[1] and stats[0]"""
+    import cbow_groups
+
+    dim, seed = 48, 53
+    idx, cum, si = bit_corpus(60, 12, 21, seed, sample)
+    n_vocab = len(cum)
+    rng = np.random.default_rng(3)
+    s0 = ((rng.random((n_vocab, dim)) - 0.5) / dim).astype(np.float32)
+    s1 = np.zeros((n_vocab, dim), np.float32)
+    stats = np.zeros(2, np.int64)
+    bases = (0, 12)
+    n = sum(cpu_train(cbow_cpu, idx, s0, s1, cum, si, n_vocab, base, seed, dim, window, negative, 0.025, 1,
+                      None, stats) for base in bases)
+    got = cbow_groups.replay(idx, cum, si, n_vocab, seed, bases, window, negative, 6, 8)
+    assert got["positions"] == n > 100
+    assert got["centre_draws"] == stats[1] > 0
+    assert got["windows_twice"] == stats[0] > 0
+    assert (got["max_kept"] < 21) == (sample > 0) and got["max_count"] <= min(2 * window, 20)
+    # the grouping changes what is counted per group, never the positions or the draws
+    other = cbow_groups.replay(idx, cum, si, n_vocab, seed, bases, window, negative, 2, 1)
+    for key in ("positions", "centre_draws", "windows_twice", "max_count", "max_kept", "max_position"):
+        assert other[key] == got[key], key
+    assert other["ctx_dup_in_group"] == 0  # groups of one context row
+    assert other["ctx_dup_across_groups"] >= got["windows_twice"]  # every such window repeats a row
 
 
 # a vocabulary of 5 words whose negative draws land on words 2 and 3 only (a draw of exactly 0, one
