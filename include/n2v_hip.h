@@ -787,7 +787,7 @@ int n2v_rank_pairs_build(const n2v_graph *g, const int32_t *rank_of, const int32
  *   mode 0  independent random reads (a hop-table gather), 4 in flight per lane; element width
  *           = row_bytes (16, 8 or 4; 0 = 16)
  *   mode 1  one dependent chain of such reads per lane (a walker)
- *   mode 2  random rows of row_bytes (512 | 1024 | 2048) read by one wave each (a syn0 row)
+ *   mode 2  random rows of row_bytes (256 | 512 | 1024 | 2048) read by one wave each (a syn0 row)
  *   mode 3  the same rows read, modified and written back (a trained row)
  *   mode 4  one dependent chain of random 4-byte reads per lane with a binary search over an LDS
  *           table of row_bytes degree classes (a power of two, 64 .. 8192) between them: a walker on
@@ -896,6 +896,38 @@ int n2v_cbow_train(const int32_t *walks, int64_t n_walks, int32_t walk_len,
 /* The waves n2v_cbow_train keeps in flight for such a launch on this device (nothing is launched), or
  * a negative status for parameters it would refuse. */
 int64_t n2v_cbow_hogwild_waves(const n2v_sgns_params *P, int64_t n_walks, int32_t walk_len);
+
+/* Link prediction over trained vectors (node2vec paper, section 4.4; csrc/n2v_pairs.hip, DESIGN.md "Link
+ * prediction").  ADDITIONS ONLY: nothing that existed changes and N2V_ABI_VERSION stays 15, as when CBOW was
+ * added.  X: row-major fp32 [n, dim], 1 <= dim <= 1024, 0 <= n < 2^31; a, b: [n_pairs] int64 row numbers.
+ * All three calls only read X and the graph.  Argument errors are N2V_EINVAL before any launch (sizes, an
+ * unknown metric / op, an n_pairs whose grid of ceil(n_pairs / 256) blocks does not fit, then NULL pointers);
+ * n_pairs == 0 is N2V_OK and launches nothing.  A pair with an index outside [0, n) (outside
+ * [0, n_vertices) for n2v_pairs_in_graph) is never dereferenced: its score or feature row is NaN, its
+ * mask 0. */
+#define N2V_PAIR_DOT 0    /* dot(x_a, x_b) */
+#define N2V_PAIR_COSINE 1 /* dot(x_a, x_b) * (inv_norm[a] * inv_norm[b]) */
+/* the binary operators of the paper's Table 1, element by element */
+#define N2V_PAIR_AVERAGE 0  /* (x_a + x_b) * 0.5f */
+#define N2V_PAIR_HADAMARD 1 /* x_a * x_b */
+#define N2V_PAIR_L1 2       /* fabsf(x_a - x_b) */
+#define N2V_PAIR_L2 3       /* (x_a - x_b) * (x_a - x_b) */
+
+/* out_scores[i] = score of (a[i], b[i]), fp32 [n_pairs].  inv_norm: the output of n2v_knn_inv_norms,
+ * required for N2V_PAIR_COSINE, ignored (may be NULL) for N2V_PAIR_DOT; a zero row scores 0, NaN or inf
+ * propagates, as in n2v_knn_*.  The dot is summed by fp32 fmaf and adds in ONE fixed order that depends on
+ * dim alone (written out in csrc/n2v_pairs.hip and restated in tests/cpu_pairs/n2v_pairs_cpu.c): not on
+ * n_pairs, the pair's place in the list or the launch; and score(a, b) == score(b, a) bit for bit. */
+int n2v_pair_scores(const float *X, const float *inv_norm, int64_t n, int32_t dim, const int64_t *a,
+                    const int64_t *b, int64_t n_pairs, int32_t metric, float *out_scores, void *stream);
+/* out[i, :] = op(x_a[i], x_b[i]), fp32 [n_pairs, dim] row-major: one or two correctly rounded fp32
+ * operations per element, no contraction (bit-identical to numpy float32).  64-bit offsets throughout. */
+int n2v_pair_features(const float *X, int64_t n, int32_t dim, const int64_t *a, const int64_t *b,
+                      int64_t n_pairs, int32_t op, float *out, void *stream);
+/* out_mask[i] = 1 if row a[i] of the CSR (rowptr int64 [n_vertices + 1], col int32, ascending within a
+ * row, multi-edges adjacent, empty rows allowed) holds b[i], else 0.  uint8 [n_pairs]. */
+int n2v_pairs_in_graph(const int64_t *rowptr, const int32_t *col, int64_t n_vertices, const int64_t *a,
+                       const int64_t *b, int64_t n_pairs, uint8_t *out_mask, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,304 @@
+// n2v_pairs.hip -- link prediction over trained vectors (the node2vec paper's section 4.4): for a list of
+// vertex pairs (a[i], b[i]) the score of every pair, the paper's four edge features (its Table 1), and
+// whether the pair is an edge of a CSR graph.  Read-only on X and on the graph; nothing is allocated, no
+// atomics, no LDS, no grid cap: a wave owns 64 consecutive pairs, a block of four waves 256, and the grid is
+// ceil(n_pairs / 256).
+//
+// The score's fixed order (DESIGN.md "Link prediction"; tests/cpu_pairs/n2v_pairs_cpu.c restates it).  It
+// depends on dim alone:
+//   G = 16 for dim <= 128, 32 for dim <= 256, 64 beyond           (the lanes that share one pair)
+//   lane l of the G:  s_l = +0;  for c = l, l + G, l + 2 G, ... while 4 c < dim:
+//                       for j = 0 .. 3 while 4 c + j < dim:  s_l = fmaf(x_a[4 c + j], x_b[4 c + j], s_l)
+//   then for off = 1, 2, 4, ... < G, in every lane at once:       s_l = s_l + s_(l xor off)
+//   dot = s_0 (every lane holds the same bits: fp32 addition commutes)
+// fmaf and + commute in their two operands, so dot(a, b) and dot(b, a) are the same bits, and the cosine is
+// written dot * (inv_norm[a] * inv_norm[b]) for the same reason.  A pair's place in the list, the number of
+// pairs and the launch geometry do not enter.
+//
+// Shape: the gather is the cost (2 * 4 * dim bytes of randomly placed rows per pair), so a lane group of G
+// lanes reads a row in 16-byte pieces, 64 / G pairs side by side in a wave and U of those steps unrolled:
+// eight 16-byte loads per lane are issued before the first is used.  Pair indices are loaded one lane per
+// pair and broadcast by lane shuffles; scores leave as one contiguous 256-byte run per wave; feature rows
+// leave as 16-byte non-temporal stores (they are written once and not read here).  dim % 4 != 0 or a
+// pointer that is not 16-byte aligned goes element by element through the same guards (VEC = false).
+#include <math.h>
+
+#include "n2v_common.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kWavePairs = 64;
+constexpr int kBlockPairs = 256;  // 4 waves
+
+// chunk c of a row: elements 4 c .. 4 c + 3; what lies at or beyond dim (or in a dead pair's row) reads as 0
+template <bool VEC>
+__device__ __forceinline__ f32x4 load_chunk(const float *__restrict__ row, int c, int32_t dim, bool live) {
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (VEC) {
+    if (live && 4 * c < dim) v = *reinterpret_cast<const f32x4 *>(row + 4 * c);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (live && 4 * c + j < dim) v[j] = row[4 * c + j];
+  }
+  return v;
+}
+
+// Row numbers of the wave's pairs, one lane per pair: -1 in both for a pair beyond the list or with an index
+// outside [0, n) -- such a row is never dereferenced.
+__device__ __forceinline__ void load_pair(const int64_t *__restrict__ a, const int64_t *__restrict__ b, int64_t p0,
+                                          int cnt, int64_t n, int lane, int32_t &ra, int32_t &rb) {
+  ra = rb = -1;
+  if (lane < cnt) {
+    const int64_t ia = a[p0 + lane], ib = b[p0 + lane];
+    if (ia >= 0 && ia < n && ib >= 0 && ib < n) ra = (int32_t)ia, rb = (int32_t)ib;
+  }
+}
+
+// pairs per step of a wave: 64 / G side by side, U steps unrolled
+template <int K>
+struct Unroll { static constexpr int U = K == 1 ? 4 : K == 2 ? 2 : 1; };
+
+// The U x K chunks of both rows of this lane's pairs of the step starting at pair `base` of the wave; all
+// loads are issued before any is used.  live[u]: the pair exists and both indices are rows.
+template <int G, int K, bool VEC>
+__device__ __forceinline__ void load_step(const float *__restrict__ X, int32_t dim, int32_t ra, int32_t rb, int base,
+                                          int lane, f32x4 (&va)[Unroll<K>::U][K], f32x4 (&vb)[Unroll<K>::U][K],
+                                          bool (&live)[Unroll<K>::U]) {
+  constexpr int GP = 64 / G, U = Unroll<K>::U;
+  const int g = lane / G, l = lane % G;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int q = base + u * GP + g;  // < 64: the step divides the wave's pairs
+    const int32_t xa = __shfl(ra, q, 64), xb = __shfl(rb, q, 64);
+    live[u] = xa >= 0;
+    const float *pa = X + (int64_t)(live[u] ? xa : 0) * dim;
+    const float *pb = X + (int64_t)(live[u] ? xb : 0) * dim;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      va[u][k] = load_chunk<VEC>(pa, l + k * G, dim, live[u]);
+      vb[u][k] = load_chunk<VEC>(pb, l + k * G, dim, live[u]);
+    }
+  }
+}
+
+template <int G, int K, bool VEC>
+__global__ __launch_bounds__(256) void pair_scores_kernel(const float *__restrict__ X,
+                                                          const float *__restrict__ inv_norm, int64_t n, int32_t dim,
+                                                          const int64_t *__restrict__ a,
+                                                          const int64_t *__restrict__ b, int64_t n_pairs,
+                                                          float *__restrict__ out) {
+  constexpr int GP = 64 / G, U = Unroll<K>::U;
+  const int lane = threadIdx.x & 63;
+  const int64_t p0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * kWavePairs;
+  if (p0 >= n_pairs) return;
+  const int cnt = n_pairs - p0 < kWavePairs ? (int)(n_pairs - p0) : kWavePairs;
+  int32_t ra, rb;
+  load_pair(a, b, p0, cnt, n, lane, ra, rb);
+  float scale = 1.f;
+  if (inv_norm && ra >= 0) scale = inv_norm[ra] * inv_norm[rb];
+  const int l = lane % G;
+  float res = 0.f;
+  for (int base = 0; base < cnt; base += GP * U) {
+    f32x4 va[U][K], vb[U][K];
+    bool live[U];
+    load_step<G, K, VEC>(X, dim, ra, rb, base, lane, va, vb, live);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      float s = 0.f;
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const int c = l + k * G;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (4 * c + j < dim) s = __fmaf_rn(va[u][k][j], vb[u][k][j], s);
+      }
+#pragma unroll
+      for (int off = 1; off < G; off <<= 1) s += __shfl_xor(s, off, 64);
+      // the GP dots of this step go to the lanes that own those pairs
+      const int d = lane - (base + u * GP);
+      const float t = __shfl(s, (d & (GP - 1)) * G, 64);
+      if (d >= 0 && d < GP) res = t;
+    }
+  }
+  if (lane < cnt) out[p0 + lane] = ra < 0 ? NAN : inv_norm ? res * scale : res;
+}
+
+// one element of an edge feature: one or two correctly rounded fp32 operations (the library is built with
+// -ffp-contract=off)
+__device__ __forceinline__ float feature(int32_t op, float x, float y) {
+  switch (op) {
+    case N2V_PAIR_AVERAGE: return (x + y) * 0.5f;
+    case N2V_PAIR_HADAMARD: return x * y;
+    case N2V_PAIR_L1: return fabsf(x - y);
+    default: { const float d = x - y; return d * d; }
+  }
+}
+
+template <int G, int K, bool VEC>
+__global__ __launch_bounds__(256) void pair_features_kernel(const float *__restrict__ X, int64_t n, int32_t dim,
+                                                            const int64_t *__restrict__ a,
+                                                            const int64_t *__restrict__ b, int64_t n_pairs,
+                                                            int32_t op, float *__restrict__ out) {
+  constexpr int GP = 64 / G, U = Unroll<K>::U;
+  const int lane = threadIdx.x & 63;
+  const int64_t p0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * kWavePairs;
+  if (p0 >= n_pairs) return;
+  const int cnt = n_pairs - p0 < kWavePairs ? (int)(n_pairs - p0) : kWavePairs;
+  int32_t ra, rb;
+  load_pair(a, b, p0, cnt, n, lane, ra, rb);
+  const int g = lane / G, l = lane % G;
+  for (int base = 0; base < cnt; base += GP * U) {
+    f32x4 va[U][K], vb[U][K];
+    bool live[U];
+    load_step<G, K, VEC>(X, dim, ra, rb, base, lane, va, vb, live);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int q = base + u * GP + g;
+      if (q >= cnt) continue;
+      float *o = out + (p0 + q) * (int64_t)dim;
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const int c = l + k * G;
+        f32x4 r;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r[j] = live[u] ? feature(op, va[u][k][j], vb[u][k][j]) : NAN;
+        if (VEC) {
+          if (4 * c < dim) __builtin_nontemporal_store(r, reinterpret_cast<f32x4 *>(o + 4 * c));
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (4 * c + j < dim) o[4 * c + j] = r[j];
+        }
+      }
+    }
+  }
+}
+
+// out_mask[i] = row a[i] of the CSR holds b[i]: one lane per pair, a binary search in the row (col ascends
+// within a row, multi-edges adjacent)
+__global__ __launch_bounds__(256) void pairs_in_graph_kernel(const int64_t *__restrict__ rowptr,
+                                                             const int32_t *__restrict__ col, int64_t n_vertices,
+                                                             const int64_t *__restrict__ a,
+                                                             const int64_t *__restrict__ b, int64_t n_pairs,
+                                                             uint8_t *__restrict__ out_mask) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_pairs) return;
+  const int64_t u = a[i], v = b[i];
+  uint8_t hit = 0;
+  if (u >= 0 && u < n_vertices && v >= 0 && v < n_vertices) {
+    int64_t lo = rowptr[u];
+    const int64_t end = rowptr[u + 1];
+    int64_t hi = end;
+    while (lo < hi) {
+      const int64_t mid = lo + ((hi - lo) >> 1);
+      if ((int64_t)col[mid] < v)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    hit = lo < end && (int64_t)col[lo] == v;
+  }
+  out_mask[i] = hit;
+}
+
+// lane group and chunks per lane of a dimension (the file header's G; K = ceil(dim / 4 G))
+inline int group_of(int32_t dim) { return dim <= 128 ? 16 : dim <= 256 ? 32 : 64; }
+
+bool grid_of(int64_t n_pairs, unsigned &blocks) {
+  const int64_t g = (n_pairs + kBlockPairs - 1) / kBlockPairs;
+  if (g > 0x7fffffffLL) return false;
+  blocks = (unsigned)g;
+  return true;
+}
+
+template <int G, int K>
+void launch_scores(bool vec, unsigned blocks, hipStream_t st, const float *X, const float *inv_norm, int64_t n,
+                   int32_t dim, const int64_t *a, const int64_t *b, int64_t n_pairs, float *out) {
+  if (vec)
+    hipLaunchKernelGGL((pair_scores_kernel<G, K, true>), dim3(blocks), dim3(256), 0, st, X, inv_norm, n, dim, a, b,
+                       n_pairs, out);
+  else
+    hipLaunchKernelGGL((pair_scores_kernel<G, K, false>), dim3(blocks), dim3(256), 0, st, X, inv_norm, n, dim, a, b,
+                       n_pairs, out);
+}
+
+template <int G, int K>
+void launch_features(bool vec, unsigned blocks, hipStream_t st, const float *X, int64_t n, int32_t dim,
+                     const int64_t *a, const int64_t *b, int64_t n_pairs, int32_t op, float *out) {
+  if (vec)
+    hipLaunchKernelGGL((pair_features_kernel<G, K, true>), dim3(blocks), dim3(256), 0, st, X, n, dim, a, b, n_pairs,
+                       op, out);
+  else
+    hipLaunchKernelGGL((pair_features_kernel<G, K, false>), dim3(blocks), dim3(256), 0, st, X, n, dim, a, b,
+                       n_pairs, op, out);
+}
+
+bool sizes_ok(int64_t n, int32_t dim, int64_t n_pairs) {
+  return dim >= 1 && dim <= 1024 && n >= 0 && n < ((int64_t)1 << 31) && n_pairs >= 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int n2v_pair_scores(const float *X, const float *inv_norm, int64_t n, int32_t dim, const int64_t *a,
+                    const int64_t *b, int64_t n_pairs, int32_t metric, float *out_scores, void *stream) {
+  if (!sizes_ok(n, dim, n_pairs)) return N2V_EINVAL;
+  if (metric != N2V_PAIR_DOT && metric != N2V_PAIR_COSINE) return N2V_EINVAL;
+  if (metric == N2V_PAIR_COSINE && !inv_norm) return N2V_EINVAL;
+  unsigned blocks = 0;
+  if (!grid_of(n_pairs, blocks)) return N2V_EINVAL;
+  if (n_pairs == 0) return N2V_OK;
+  if (!X || !a || !b || !out_scores) return N2V_EINVAL;
+  if (metric == N2V_PAIR_DOT) inv_norm = nullptr;  // ignored
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = dim % 4 == 0 && ((uintptr_t)X & 15) == 0;
+  const int G = group_of(dim), K = (dim + 4 * G - 1) / (4 * G);
+  if (G == 16 && K == 1) launch_scores<16, 1>(vec, blocks, st, X, inv_norm, n, dim, a, b, n_pairs, out_scores);
+  else if (G == 16) launch_scores<16, 2>(vec, blocks, st, X, inv_norm, n, dim, a, b, n_pairs, out_scores);
+  else if (G == 32) launch_scores<32, 2>(vec, blocks, st, X, inv_norm, n, dim, a, b, n_pairs, out_scores);
+  else if (K == 2) launch_scores<64, 2>(vec, blocks, st, X, inv_norm, n, dim, a, b, n_pairs, out_scores);
+  else if (K == 3) launch_scores<64, 3>(vec, blocks, st, X, inv_norm, n, dim, a, b, n_pairs, out_scores);
+  else launch_scores<64, 4>(vec, blocks, st, X, inv_norm, n, dim, a, b, n_pairs, out_scores);
+  N2V_HIP_CHECK(hipGetLastError());
+  return N2V_OK;
+}
+
+int n2v_pair_features(const float *X, int64_t n, int32_t dim, const int64_t *a, const int64_t *b, int64_t n_pairs,
+                      int32_t op, float *out, void *stream) {
+  if (!sizes_ok(n, dim, n_pairs)) return N2V_EINVAL;
+  if (op != N2V_PAIR_AVERAGE && op != N2V_PAIR_HADAMARD && op != N2V_PAIR_L1 && op != N2V_PAIR_L2) return N2V_EINVAL;
+  unsigned blocks = 0;
+  if (!grid_of(n_pairs, blocks)) return N2V_EINVAL;
+  if (n_pairs == 0) return N2V_OK;
+  if (!X || !a || !b || !out) return N2V_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = dim % 4 == 0 && (((uintptr_t)X | (uintptr_t)out) & 15) == 0;
+  const int G = group_of(dim), K = (dim + 4 * G - 1) / (4 * G);
+  if (G == 16 && K == 1) launch_features<16, 1>(vec, blocks, st, X, n, dim, a, b, n_pairs, op, out);
+  else if (G == 16) launch_features<16, 2>(vec, blocks, st, X, n, dim, a, b, n_pairs, op, out);
+  else if (G == 32) launch_features<32, 2>(vec, blocks, st, X, n, dim, a, b, n_pairs, op, out);
+  else if (K == 2) launch_features<64, 2>(vec, blocks, st, X, n, dim, a, b, n_pairs, op, out);
+  else if (K == 3) launch_features<64, 3>(vec, blocks, st, X, n, dim, a, b, n_pairs, op, out);
+  else launch_features<64, 4>(vec, blocks, st, X, n, dim, a, b, n_pairs, op, out);
+  N2V_HIP_CHECK(hipGetLastError());
+  return N2V_OK;
+}
+
+int n2v_pairs_in_graph(const int64_t *rowptr, const int32_t *col, int64_t n_vertices, const int64_t *a,
+                       const int64_t *b, int64_t n_pairs, uint8_t *out_mask, void *stream) {
+  if (n_vertices < 0 || n_vertices >= ((int64_t)1 << 31) || n_pairs < 0) return N2V_EINVAL;
+  unsigned blocks = 0;
+  if (!grid_of(n_pairs, blocks)) return N2V_EINVAL;
+  if (n_pairs == 0) return N2V_OK;
+  if (!rowptr || !a || !b || !out_mask) return N2V_EINVAL;  // (col may be NULL: a graph without edges)
+  hipLaunchKernelGGL(pairs_in_graph_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rowptr, col,
+                     n_vertices, a, b, n_pairs, out_mask);
+  N2V_HIP_CHECK(hipGetLastError());
+  return N2V_OK;
+}
+
+}  // extern "C"

@@ -4,7 +4,7 @@
 //
 //   mode 0  independent random 16-byte reads, 4 in flight per lane -- a hop-table gather (K2)
 //   mode 1  one dependent chain of random 16-byte reads per lane     -- a walker (K2)
-//   mode 2  random rows of `row_bytes` read by one wave, 8 bytes per lane at 512 bytes, four rows
+//   mode 2  random rows of `row_bytes` read by one wave, 4 bytes per lane at 256, 8 at 512 bytes, four rows
 //           in flight                                              -- a syn0 / syn1neg row (K3)
 //   mode 3  the same rows read, changed and written back           -- a trained row (K3)
 //   mode 4  one dependent chain of random 4-byte reads per lane with a binary search over an LDS
@@ -122,14 +122,23 @@ __global__ __launch_bounds__(256) void probe_rows_kernel(float *t, uint64_t n_ro
                                                          int iters, uint32_t *sink) {
   const int lane = threadIdx.x & 63;
   const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int per_lane = row_floats / 64;  // 2 at 512-byte rows (float2 per lane), 4 at 1024
+  const int per_lane = row_floats / 64;  // 1 at 256-byte rows, 2 at 512 (float2 per lane), 4 at 1024
   float acc = 0.0f;
   for (int k = 0; k < iters; k += 4) {  // four rows in flight per wave
     float *rp[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u)
       rp[u] = t + (mix64(wave * 0x100000001B3ULL + (uint64_t)(k + u)) % n_rows) * (uint64_t)row_floats;
-    if (per_lane == 2) {
+    if (per_lane == 1) {
+      float a[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) a[u] = rp[u][lane];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        acc += a[u];
+        if (kWrite) rp[u][lane] = a[u] + 1.0f;
+      }
+    } else if (per_lane == 2) {
       float2 a[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) a[u] = reinterpret_cast<const float2 *>(rp[u])[lane];
@@ -217,7 +226,7 @@ extern "C" int n2v_mem_probe(void *buffer, int64_t buffer_bytes, int32_t mode, i
       hipLaunchKernelGGL(n2v::probe_gather_kernel<uint32_t>, dim3((unsigned)blocks), dim3(threads), 0,
                          st, (const uint32_t *)buffer, n_el, iters, mode, sink);
   } else {
-    if (row_bytes != 512 && row_bytes != 1024 && row_bytes != 2048) return N2V_EINVAL;
+    if (row_bytes != 256 && row_bytes != 512 && row_bytes != 1024 && row_bytes != 2048) return N2V_EINVAL;
     const uint64_t n_rows = (uint64_t)(buffer_bytes / row_bytes);
     if (n_rows < 2) return N2V_EINVAL;
     const void *fn = mode == 2 ? (const void *)n2v::probe_rows_kernel<false>

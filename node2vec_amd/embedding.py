@@ -293,6 +293,44 @@ class KeyedVectors:
         return similarity.knn(self._device_vectors(), topn, rows=rows, restrict=restrict_vocab,
                               inv_norm=self._inv_norm, exclude_self=exclude_self)
 
+    def _rows_of_tokens(self, tokens) -> np.ndarray:
+        """rows int64 of a sequence of tokens (ints stand for their decimal strings); KeyError for an unknown one"""
+        if isinstance(tokens, (str, int, np.integer)):
+            tokens = [tokens]
+        return np.fromiter((self._row_of(t) for t in tokens), dtype=np.int64)
+
+    def _pair_rows(self, tokens_a, tokens_b):
+        """the rows of two token lists of one length: looked up (KeyError) and checked (ValueError) before the GPU
+        is touched"""
+        ra, rb = self._rows_of_tokens(tokens_a), self._rows_of_tokens(tokens_b)
+        if ra.shape[0] != rb.shape[0]:
+            raise ValueError(f"tokens_a and tokens_b must have the same length, not {ra.shape[0]} and {rb.shape[0]}")
+        return ra, rb
+
+    def pair_scores(self, tokens_a, tokens_b, metric: str = "cosine") -> np.ndarray:
+        """score of every pair (tokens_a[i], tokens_b[i]), fp32 [n]: "cosine" (gensim's similarity, over the cached
+        init_sims norms) or "dot" (csrc/n2v_pairs.hip; every score in one fixed order, symmetric in the pair)"""
+        from node2vec_amd import linkpred
+
+        if metric not in linkpred.METRICS:
+            raise ValueError(f"metric {metric!r}: " + " | ".join(linkpred.METRICS))
+        ra, rb = self._pair_rows(tokens_a, tokens_b)
+        X = self._device_vectors()
+        if metric == "cosine":
+            self.init_sims()
+        return linkpred.pair_scores(X, torch.from_numpy(ra), torch.from_numpy(rb), metric,
+                                    inv_norm=self._inv_norm).cpu().numpy()
+
+    def edge_features(self, tokens_a, tokens_b, op: str = "hadamard") -> np.ndarray:
+        """the node2vec paper's edge feature of every pair, fp32 [n, dim]: "average" | "hadamard" | "l1" | "l2" """
+        from node2vec_amd import linkpred
+
+        if op not in linkpred.OPERATORS:
+            raise ValueError(f"operator {op!r}: " + " | ".join(linkpred.OPERATORS))
+        ra, rb = self._pair_rows(tokens_a, tokens_b)
+        return linkpred.pair_features(self._device_vectors(), torch.from_numpy(ra), torch.from_numpy(rb),
+                                      op).cpu().numpy()
+
     @classmethod
     def load_word2vec_format(cls, fname: str) -> "KeyedVectors":
         with open(fname) as f:
@@ -343,7 +381,32 @@ def _check_objective(p: Dict[str, Any]) -> None:
         raise ValueError("batched is a skip-gram trainer: not available with sg=0 (CBOW)")
 
 
-class Node2VecHIP(Node2VecBase):
+class _PairQueries:
+    """link_scores() / edge_embedding() of a fitted model: what Node2VecHIP and Node2VecSpark share.  `df_edges`
+    holds vertex ids in columns "src" and "dst"; an id outside the vocabulary is a KeyError."""
+
+    model = None
+
+    def _edge_ids(self, df_edges: pd.DataFrame):
+        if self.model is None:
+            raise ValueError("Model is not available. Please run fit()")
+        if "src" not in df_edges.columns or "dst" not in df_edges.columns:
+            raise ValueError('df_edges must have the columns "src" and "dst"')
+        return df_edges["src"].to_numpy(), df_edges["dst"].to_numpy()
+
+    def link_scores(self, df_edges: pd.DataFrame, metric: str = "cosine") -> pd.DataFrame:
+        """["src", "dst", "score"]: the score of every row's pair of vertices (model.wv.pair_scores)"""
+        src, dst = self._edge_ids(df_edges)
+        return pd.DataFrame({"src": src, "dst": dst, "score": self.model.wv.pair_scores(src, dst, metric)})
+
+    def edge_embedding(self, df_edges: pd.DataFrame, operator: str = "hadamard") -> pd.DataFrame:
+        """["src", "dst", "vector"]: the edge feature of every row's pair of vertices (model.wv.edge_features)"""
+        src, dst = self._edge_ids(df_edges)
+        vectors = corpus.list_column(self.model.wv.edge_features(src, dst, operator))
+        return pd.DataFrame({"src": src, "dst": dst, "vector": vectors})
+
+
+class Node2VecHIP(Node2VecBase, _PairQueries):
     """Drop-in for Node2VecGensim (embedding.py:70-178) on one MI355X."""
 
     def __init__(
@@ -590,7 +653,7 @@ HIP_HS_PARAMS: Dict[str, Any] = {
 }
 
 
-class Node2VecSpark(Node2VecBase):
+class Node2VecSpark(Node2VecBase, _PairQueries):
     """Drop-in for the reference's Node2VecSpark (embedding.py:182-285) on one MI355X: skip-gram with
     hierarchical softmax, what Spark ML's Word2Vec trains (node2vec_amd/hs.py, csrc/n2v_hs.hip).
 
