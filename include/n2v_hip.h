@@ -929,6 +929,44 @@ int n2v_pair_features(const float *X, int64_t n, int32_t dim, const int64_t *a, 
 int n2v_pairs_in_graph(const int64_t *rowptr, const int32_t *col, int64_t n_vertices, const int64_t *a,
                        const int64_t *b, int64_t n_pairs, uint8_t *out_mask, void *stream);
 
+/* k-means (Lloyd) over trained vectors (the node2vec paper's case study, section 4.1; csrc/n2v_kmeans.hip,
+ * DESIGN.md "Clustering").  ADDITIONS ONLY: N2V_ABI_VERSION stays 15.  X: row-major fp32 [n, dim],
+ * 1 <= dim <= 1024, 0 <= n < 2^31; centroids: fp32 [k, dim], 1 <= k <= 1024; labels: int32 [n], -1 = no
+ * cluster; inv_norm: the output of n2v_knn_inv_norms, required for N2V_KMEANS_COSINE, ignored otherwise.
+ * Every result is a function of the arguments alone, bit for bit (no float atomics; the orders are written
+ * out in csrc/n2v_kmeans.hip and restated in tests/cpu_kmeans/n2v_kmeans_cpu.c).  Argument errors are
+ * N2V_EINVAL before any launch: sizes or metric out of range, cosine without inv_norm, then (n > 0) a NULL
+ * required pointer, a workspace that is NULL, not 16-byte aligned or smaller than
+ * n2v_kmeans_workspace_bytes, centroids_out == the input centroids.  n == 0 is N2V_OK and launches nothing. */
+#define N2V_KMEANS_EUCLIDEAN 0 /* t(c, r) = fmaf(-2, dot(c, r), sum c^2);  dist = fmaxf(t_min + sum x_r^2, 0) */
+#define N2V_KMEANS_COSINE 1    /* unit centroids: t(c, r) = -dot(c, r);  dist = 1 - dot_best * inv_norm[r] */
+
+/* Rows per slab of the update's fixed order of summation (a multiple of 64; -1 for sizes the calls refuse):
+ * round_up(ceil(n / S), 64) with S = min(2048, 512 MiB / (4 k dim)) slabs at most. */
+int64_t n2v_kmeans_slab_rows(int64_t n, int32_t dim, int32_t k);
+/* Bytes of workspace of the three calls below (-1 for sizes they refuse, 0 for n == 0): the padded centroids
+ * and their squared norms, 4 round_up(k, 64) (round_up(dim, 16) + 1), plus one fp32 [k, dim] partial sum per
+ * slab, 4 k dim ceil(n / slab_rows) <= 512 MiB whatever n is (each part rounded up to 256 bytes). */
+int64_t n2v_kmeans_workspace_bytes(int64_t n, int32_t dim, int32_t k);
+/* labels_out[r] = the lowest c with the smallest t(c, r); a row whose every t is NaN or +inf gets -1 and
+ * dist NaN; a zero row gets label 0 and dist 1 by cosine.  dist_out: fp32 [n] or NULL. */
+int n2v_kmeans_assign(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *centroids,
+                      int32_t k, int32_t metric, int32_t *labels_out, float *dist_out, void *workspace,
+                      int64_t workspace_bytes, void *stream);
+/* centroids_out[c] = the mean of the rows of label c (cosine: the unit vector of the sum of their unit
+ * vectors); a cluster without rows (cosine: or with a zero sum) keeps prev_centroids[c] bit for bit.
+ * counts_out: int64 [k].  A label outside [-1, k) is treated as -1 and never used as an index. */
+int n2v_kmeans_update(const float *X, const float *inv_norm, int64_t n, int32_t dim, const int32_t *labels,
+                      int32_t k, int32_t metric, const float *prev_centroids, float *centroids_out,
+                      int64_t *counts_out, void *workspace, int64_t workspace_bytes, void *stream);
+/* One Lloyd iteration that reads X once: n2v_kmeans_assign against centroids_in followed by
+ * n2v_kmeans_update with centroids_in as the previous centroids, bit for bit.  labels_inout: the previous
+ * labels in (any values), the new ones out; stats_out: int64 [2] = {labels that changed, rows left at -1}. */
+int n2v_kmeans_step(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *centroids_in,
+                    int32_t k, int32_t metric, int32_t *labels_inout, float *dist_out, float *centroids_out,
+                    int64_t *counts_out, int64_t *stats_out, void *workspace, int64_t workspace_bytes,
+                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

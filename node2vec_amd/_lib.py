@@ -18,6 +18,7 @@ WALK_EXACT, WALK_FAST = 0, 1
 WIRE_F32, WIRE_BF16 = 0, 1
 PAIR_DOT, PAIR_COSINE = 0, 1
 PAIR_AVERAGE, PAIR_HADAMARD, PAIR_L1, PAIR_L2 = 0, 1, 2, 3
+KMEANS_EUCLIDEAN, KMEANS_COSINE = 0, 1
 
 # every symbol include/n2v_hip.h declares
 SYMBOLS = ("n2v_abi_version", "n2v_status_string", "n2v_device_count", "n2v_alias_build",
@@ -32,7 +33,8 @@ SYMBOLS = ("n2v_abi_version", "n2v_status_string", "n2v_device_count", "n2v_alia
            "n2v_wedge_slots_fold", "n2v_edge_row_sums_build", "n2v_knn_inv_norms", "n2v_knn_workspace_bytes",
            "n2v_knn_topk", "n2v_knn_scores", "n2v_hs_tree_build", "n2v_hs_train", "n2v_hs_hogwild_waves",
            "n2v_rank_pairs_build", "n2v_cbow_train", "n2v_cbow_hogwild_waves", "n2v_pair_scores",
-           "n2v_pair_features", "n2v_pairs_in_graph")
+           "n2v_pair_features", "n2v_pairs_in_graph", "n2v_kmeans_slab_rows", "n2v_kmeans_workspace_bytes",
+           "n2v_kmeans_assign", "n2v_kmeans_update", "n2v_kmeans_step")
 
 
 class WeightedHubs(C.Structure):
@@ -248,6 +250,20 @@ def load():
     L.n2v_pairs_in_graph.restype = C.c_int
     L.n2v_pairs_in_graph.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p]
+    L.n2v_kmeans_slab_rows.restype = C.c_int64
+    L.n2v_kmeans_slab_rows.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    L.n2v_kmeans_workspace_bytes.restype = C.c_int64
+    L.n2v_kmeans_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    L.n2v_kmeans_assign.restype = C.c_int
+    L.n2v_kmeans_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.n2v_kmeans_update.restype = C.c_int
+    L.n2v_kmeans_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.n2v_kmeans_step.restype = C.c_int
+    L.n2v_kmeans_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                  C.c_void_p]
     _lib = L
     return L
 

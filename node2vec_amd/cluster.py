@@ -1,0 +1,251 @@
+"""k-means over trained vectors, on the GPU (csrc/n2v_kmeans.hip): the clustering of the node2vec paper's case
+study (section 4.1), without copying the matrix to the host.
+
+Lloyd's iteration with one pass over X per iteration (n2v_kmeans_step scores, assigns and sums in one launch).
+"euclidean" is what the paper and scikit-learn use and is the default HERE, as in scikit-learn; "cosine" is
+spherical k-means (unit centroids, rows weighted by 1 / norm) and is the default on KeyedVectors.kmeans and the
+model classes, whose other queries are all cosines.  Every label, distance and centroid is computed in one fixed
+order of fp32 / fp64 operations (DESIGN.md "Clustering"): the same call gives the same bits, whatever the launch.
+A cluster that loses all its rows keeps its centroid (scikit-learn relocates it).  A row whose distances are all
+NaN gets label -1, joins no cluster and is counted in n_unassigned.
+
+Device tensors in and out.  There is no CPU path: a missing GPU or library raises.
+"""
+from typing import NamedTuple, Optional, Tuple
+
+import numpy as np
+import torch
+
+from node2vec_amd import _lib, similarity
+
+METRICS = {"euclidean": _lib.KMEANS_EUCLIDEAN, "cosine": _lib.KMEANS_COSINE}
+INITS = ("k-means++", "random")
+MAX_K = 1024
+
+
+class KMeansResult(NamedTuple):
+    centroids: torch.Tensor  # fp32 [k, dim] (unit vectors for cosine)
+    labels: torch.Tensor     # int32 [n], -1: unassigned
+    dist: torch.Tensor       # fp32 [n]: squared Euclidean distance, or 1 - cosine, to the row's centroid
+    counts: torch.Tensor     # int64 [k]
+    inertia: float           # dist.double().sum() over the assigned rows
+    n_iter: int
+    converged: bool
+    n_unassigned: int
+
+
+def _check_metric(metric: str) -> None:
+    if metric not in METRICS:
+        raise ValueError(f"metric {metric!r}: " + " | ".join(METRICS))
+
+
+def _check_k(k, n: Optional[int] = None) -> int:
+    k = int(k)
+    if k < 1 or k > MAX_K:
+        raise ValueError(f"k = {k} outside [1, {MAX_K}]")
+    if n is not None and k > n:
+        raise ValueError(f"k = {k} clusters of n = {n} rows")
+    return k
+
+
+def _shape(X) -> Tuple[int, int]:
+    if not isinstance(X, torch.Tensor) or X.ndim != 2:
+        raise ValueError("X must be a 2-D tensor on a HIP device")
+    return int(X.shape[0]), int(X.shape[1])
+
+
+def _norms(X: torch.Tensor, metric: str, inv_norm: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    if metric != "cosine":
+        return None
+    if inv_norm is None:
+        return similarity.inv_norms(X)
+    if inv_norm.ndim != 1 or inv_norm.shape[0] < X.shape[0]:
+        raise ValueError("inv_norm must hold one value per row of X")
+    return inv_norm[:X.shape[0]].to(device=X.device, dtype=torch.float32).contiguous()
+
+
+def _centroids(C, k: Optional[int], dim: int) -> torch.Tensor:
+    """the shape of a centroid matrix, checked on the host"""
+    if not isinstance(C, torch.Tensor) or C.ndim != 2 or C.shape[1] != dim or (k is not None and C.shape[0] != k):
+        raise ValueError(f"centroids must be a [{'k' if k is None else k}, {dim}] tensor")
+    if not 1 <= C.shape[0] <= MAX_K:
+        raise ValueError(f"k = {C.shape[0]} outside [1, {MAX_K}]")
+    return C
+
+
+def _workspace(n: int, dim: int, k: int, device) -> torch.Tensor:
+    need = int(_lib.load().n2v_kmeans_workspace_bytes(n, dim, k))
+    return torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _unit(C: torch.Tensor) -> torch.Tensor:
+    return C * similarity.inv_norms(C)[:, None]
+
+
+def slab_rows(n: int, dim: int, k: int) -> int:
+    """rows per slab of the update's fixed order of summation (n2v_kmeans_slab_rows)"""
+    return int(_lib.load().n2v_kmeans_slab_rows(n, dim, k))
+
+
+def assign(X: torch.Tensor, centroids: torch.Tensor, metric: str = "euclidean",
+           inv_norm: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(labels int32 [n], dist fp32 [n]): the nearest centroid of every row (ties: the lowest index) and the
+    distance to it -- squared Euclidean, or 1 - cosine against UNIT centroids (init_centroids and update return
+    such).  inv_norm: similarity.inv_norms(X) for cosine, computed when not given."""
+    _check_metric(metric)
+    n, dim = _shape(X)
+    _centroids(centroids, None, dim)
+    X = similarity._matrix(X)
+    C = centroids.to(device=X.device, dtype=torch.float32).contiguous()
+    k = C.shape[0]
+    norms = _norms(X, metric, inv_norm)
+    labels = torch.empty(n, dtype=torch.int32, device=X.device)
+    dist = torch.empty(n, dtype=torch.float32, device=X.device)
+    with torch.cuda.device(X.device):
+        ws = _workspace(n, dim, k, X.device)
+        _lib.check(_lib.load().n2v_kmeans_assign(X.data_ptr(), _ptr(norms), n, dim, C.data_ptr(), k, METRICS[metric],
+                                                 labels.data_ptr(), dist.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                 _lib.current_stream_ptr()), "n2v_kmeans_assign")
+    return labels, dist
+
+
+def update(X: torch.Tensor, labels: torch.Tensor, k: int, metric: str, prev_centroids: torch.Tensor,
+           inv_norm: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(centroids fp32 [k, dim], counts int64 [k]): the mean of every cluster's rows (cosine: the unit vector of the
+    sum of their unit vectors); an empty cluster keeps its row of prev_centroids.  A label outside [0, k) joins no
+    cluster."""
+    _check_metric(metric)
+    n, dim = _shape(X)
+    k = _check_k(k)
+    _centroids(prev_centroids, k, dim)
+    if not isinstance(labels, torch.Tensor) or labels.ndim != 1 or labels.shape[0] != n:
+        raise ValueError(f"labels must be a [{n}] tensor")
+    X = similarity._matrix(X)
+    prev = prev_centroids.to(device=X.device, dtype=torch.float32).contiguous()
+    labels = labels.to(device=X.device, dtype=torch.int32).contiguous()
+    norms = _norms(X, metric, inv_norm)
+    out = prev.clone()
+    counts = torch.zeros(k, dtype=torch.int64, device=X.device)
+    with torch.cuda.device(X.device):
+        ws = _workspace(n, dim, k, X.device)
+        _lib.check(_lib.load().n2v_kmeans_update(X.data_ptr(), _ptr(norms), n, dim, labels.data_ptr(), k,
+                                                 METRICS[metric], prev.data_ptr(), out.data_ptr(), counts.data_ptr(),
+                                                 ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
+                   "n2v_kmeans_update")
+    return out, counts
+
+
+def draw_next(D: torch.Tensor, rng: np.random.Generator, chosen) -> int:
+    """k-means++'s draw: a row with probability D[row] / sum(D), by one rng.random() against the float64 running
+    sum of D.  A row of D = 0 (every chosen row) cannot be drawn; when the sum is 0 the lowest row not in
+    `chosen` is taken (and no random number)."""
+    cum = torch.cumsum(D.to(torch.float64), 0)
+    total = float(cum[-1])
+    if not total > 0.0:
+        taken = set(int(c) for c in chosen)
+        return next(r for r in range(D.shape[0]) if r not in taken)
+    u = rng.random() * total
+    at = torch.searchsorted(cum, torch.tensor([u], dtype=torch.float64, device=cum.device), right=True)
+    return int(at.clamp(max=D.shape[0] - 1))
+
+
+def init_centroids(X: torch.Tensor, k: int, metric: str = "euclidean", seed: int = 0, init="k-means++",
+                   inv_norm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """k initial centroids, fp32 [k, dim] (unit vectors for cosine), from rng = numpy.random.default_rng(seed):
+    "random": k distinct rows; "k-means++" (Arthur & Vassilvitskii): the first rng.integers(n), every further one
+    drawn with probability proportional to the distance to the nearest centre chosen so far (one assign pass with
+    k = 1 per centre); or a [k, dim] tensor, used as it is (normalised for cosine).  The same seed gives the same
+    centres."""
+    _check_metric(metric)
+    n, dim = _shape(X)
+    k = _check_k(k, n)
+    if isinstance(init, torch.Tensor):
+        _centroids(init, k, dim)
+    elif init not in INITS:
+        raise ValueError(f"init {init!r}: " + " | ".join(INITS) + " | a [k, dim] tensor")
+    X = similarity._matrix(X)
+    unit = _unit if metric == "cosine" else (lambda C: C)
+    if isinstance(init, torch.Tensor):
+        return unit(init.to(device=X.device, dtype=torch.float32).contiguous().clone())
+    rng = np.random.default_rng(seed)
+    if init == "random":
+        rows = np.sort(rng.choice(n, size=k, replace=False))
+        return unit(X[torch.from_numpy(rows).to(X.device)].contiguous())
+    norms = _norms(X, metric, inv_norm)
+    chosen = [int(rng.integers(n))]
+    D = None
+    for _ in range(1, k):
+        centre = unit(X[chosen[-1]:chosen[-1] + 1].contiguous())
+        dist = torch.nan_to_num(assign(X, centre, metric, norms)[1], nan=0.0, posinf=0.0)
+        D = dist if D is None else torch.minimum(D, dist)
+        D[chosen] = 0.0
+        chosen.append(draw_next(D, rng, chosen))
+    return unit(X[torch.tensor(chosen, device=X.device)].contiguous())
+
+
+def _lloyd(X, norms, C, metric, max_iter, tol) -> KMeansResult:
+    L = _lib.load()
+    n, dim = X.shape
+    k = C.shape[0]
+    labels = torch.full((n,), -1, dtype=torch.int32, device=X.device)
+    dist = torch.empty(n, dtype=torch.float32, device=X.device)
+    nxt = torch.empty_like(C)
+    counts = torch.zeros(k, dtype=torch.int64, device=X.device)
+    stats = torch.zeros(2, dtype=torch.int64, device=X.device)
+    ws = _workspace(n, dim, k, X.device)
+    n_iter, settled, converged = 0, False, False
+    for n_iter in range(1, max_iter + 1):
+        _lib.check(L.n2v_kmeans_step(X.data_ptr(), _ptr(norms), n, dim, C.data_ptr(), k, METRICS[metric],
+                                     labels.data_ptr(), dist.data_ptr(), nxt.data_ptr(), counts.data_ptr(),
+                                     stats.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
+                   "n2v_kmeans_step")
+        shift = ((nxt - C) ** 2).sum() if tol > 0 else None
+        C, nxt = nxt, C
+        n_changed = int(stats[0])  # the iteration's one synchronisation
+        if n_changed == 0:  # the labels of the iteration before: the update repeated itself bit for bit
+            settled = converged = True
+            break
+        if shift is not None and float(shift) <= tol:
+            converged = True
+            break
+    if not settled:  # labels and distances against the centroids that are returned
+        _lib.check(L.n2v_kmeans_assign(X.data_ptr(), _ptr(norms), n, dim, C.data_ptr(), k, METRICS[metric],
+                                       labels.data_ptr(), dist.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       _lib.current_stream_ptr()), "n2v_kmeans_assign")
+    live = labels >= 0
+    counts = torch.bincount(labels[live].long(), minlength=k)
+    return KMeansResult(C, labels, dist, counts, float(dist[live].double().sum()), n_iter, converged,
+                        int(n - int(live.sum())))
+
+
+def kmeans(X: torch.Tensor, k: int, metric: str = "euclidean", init="k-means++", n_init: int = 1, max_iter: int = 100,
+           tol: float = 0.0, seed: int = 0, inv_norm: Optional[torch.Tensor] = None) -> KMeansResult:
+    """Lloyd's k-means of the rows of X.  metric: "euclidean" (the default here, as in scikit-learn) or "cosine"
+    (spherical; the default of KeyedVectors.kmeans and of the model classes' cluster()).  An iteration is one
+    n2v_kmeans_step; it stops when no label changed (converged), when tol > 0 and the summed squared shift of the
+    centres is <= tol (converged), or after max_iter iterations.  Unless it stopped on unchanged labels, one more
+    assignment makes labels and dist those of the returned centroids.  n_init > 1: seeds seed, seed + 1, ...; the
+    run of lowest inertia is returned (ties: the first).  One host synchronisation per iteration."""
+    _check_metric(metric)
+    n, dim = _shape(X)
+    k = _check_k(k, n)
+    if isinstance(init, torch.Tensor):
+        _centroids(init, k, dim)
+    elif init not in INITS:
+        raise ValueError(f"init {init!r}: " + " | ".join(INITS) + " | a [k, dim] tensor")
+    if int(n_init) < 1 or int(max_iter) < 1 or not float(tol) >= 0.0:
+        raise ValueError("n_init and max_iter must be >= 1 and tol >= 0")
+    X = similarity._matrix(X)
+    norms = _norms(X, metric, inv_norm)
+    best = None
+    with torch.cuda.device(X.device):
+        for run in range(int(n_init)):
+            C = init_centroids(X, k, metric, int(seed) + run, init, norms)
+            res = _lloyd(X, norms, C, metric, int(max_iter), float(tol))
+            if best is None or res.inertia < best.inertia:
+                best = res
+    return best

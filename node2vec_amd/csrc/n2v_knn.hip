@@ -12,33 +12,18 @@
 // kernel call the same score_tile, so n2v_knn_topk's scores equal n2v_knn_scores' bit for bit.
 #include <float.h>
 
-#include "n2v_common.h"
+#include "n2v_score_tile.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kWaves = 8;              // waves per block of the top-k kernel
 constexpr int kStepRows = kWaves * 16; // rows scored per block step (16 per wave)
 constexpr int kMaxK = 1024;            // the fused path's k limit
 constexpr int kSentinelRow = 0x7fffffff;
 
-__host__ __device__ inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
-
 // the padded query matrix q_hat [nq_pad][dim_pad] at the start of the workspace (zeros in the padding):
 // a tile of G x 16 queries starting at any multiple of its 8, 16, 32 or 64 kept queries stays inside
-__host__ __device__ inline int32_t dim_pad_of(int32_t dim) { return (int32_t)round_up(dim, 16); }
 inline int64_t nq_pad_of(int64_t nq) { return round_up(nq, 64) + 16; }
-
-// sum of squares of v[0..dim) in the fixed order of the file header; the whole wave calls it
-__device__ inline float wave_sumsq(const float *__restrict__ v, int32_t dim, int lane) {
-  float s = 0.f;
-  for (int d = lane; d < dim; d += 64) s = __fmaf_rn(v[d], v[d], s);
-  for (int off = 1; off < 64; off <<= 1) s += __shfl_xor(s, off, 64);
-  return s;
-}
-
-__device__ inline float inv_sqrt_or_zero(float s) { return s > 0.f ? 1.f / sqrtf(s) : 0.f; }
 
 __global__ __launch_bounds__(256) void inv_norm_kernel(const float *__restrict__ X, int64_t n, int32_t dim,
                                                        float *__restrict__ inv_norm) {
@@ -75,51 +60,6 @@ __global__ __launch_bounds__(256) void queries_kernel(const float *__restrict__ 
     inv = inv_sqrt_or_zero(wave_sumsq(v, dim, lane));
   }
   for (int d = lane; d < dp; d += 64) out[d] = d < dim ? v[d] * inv : 0.f;
-}
-
-// Dot products of 16 rows (row0 ..) with G groups of 16 queries, one wave: acc[g][i] is
-// dot(q_hat[16 g + (lane & 15)], x[row0 + 4 (lane >> 4) + i]).  The X tile is operand A (lane l:
-// row l & 15, k = l >> 4), q_hat operand B (query l & 15, k = l >> 4); a lane loads d0 + 4 k .. + 3 and
-// feeds them to four MFMAs, so d is summed in the order d0 + 4 k + j over (d0, j, k) -- fixed.
-// Rows at or beyond `row_end` and dims at or beyond `dim` read as 0.
-template <int G, bool VEC>
-__device__ inline void score_tile(const float *__restrict__ X, int32_t dim, int64_t row0, int64_t row_end,
-                                  const float *__restrict__ qhat_tile, int lane, f32x4 (&acc)[G]) {
-  const int32_t dp = dim_pad_of(dim);
-  const int64_t row = row0 + (lane & 15);
-  const bool live = row < row_end;
-  const float *xr = X + (live ? row : 0) * (int64_t)dim;
-  const int k4 = 4 * (lane >> 4);
-  const float *qb = qhat_tile + (int64_t)(lane & 15) * dp + k4;
-#pragma unroll
-  for (int g = 0; g < G; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-  constexpr int kBatch = 8;  // X loads in flight per lane: 8 x 16 B
-  for (int db = 0; db < dp; db += 16 * kBatch) {
-    f32x4 xa[kBatch];
-#pragma unroll
-    for (int b = 0; b < kBatch; ++b) {
-      const int d = db + 16 * b + k4;
-      if (VEC) {
-        xa[b] = (live && d < dim) ? *reinterpret_cast<const f32x4 *>(xr + d) : f32x4{0.f, 0.f, 0.f, 0.f};
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) xa[b][j] = (live && d + j < dim) ? xr[d + j] : 0.f;
-      }
-    }
-#pragma unroll
-    for (int b = 0; b < kBatch; ++b) {
-      const int d0 = db + 16 * b;
-      if (d0 >= dp) break;
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const f32x4 q4 = *reinterpret_cast<const f32x4 *>(qb + (int64_t)g * 16 * dp + d0);
-        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[b].x, q4.x, acc[g], 0, 0, 0);
-        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[b].y, q4.y, acc[g], 0, 0, 0);
-        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[b].z, q4.z, acc[g], 0, 0, 0);
-        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[b].w, q4.w, acc[g], 0, 0, 0);
-      }
-    }
-  }
 }
 
 // the order of results: score descending, then row ascending (empty slots: -inf, kSentinelRow)

@@ -1,0 +1,73 @@
+// n2v_score_tile.h -- the fixed-order fp32 pieces n2v_knn.hip and n2v_kmeans.hip share: the sum of
+// squares of a row (wave_sumsq), 1 / sqrt or 0, and the 16 x 16 MFMA dot chain (score_tile).  Every
+// caller gets the same bits from the same code (DESIGN.md "Nearest neighbours", "Clustering").
+#pragma once
+
+#include "n2v_common.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__host__ __device__ inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
+
+// rows of the padded operand matrix [rows_pad][dim_pad] are dim_pad floats long (zeros in the padding)
+__host__ __device__ inline int32_t dim_pad_of(int32_t dim) { return (int32_t)round_up(dim, 16); }
+
+// sum of squares of v[0..dim) in one fixed order: lane l sums d = l, l + 64, ... by fmaf, then a fixed
+// butterfly; the whole wave calls it
+__device__ inline float wave_sumsq(const float *__restrict__ v, int32_t dim, int lane) {
+  float s = 0.f;
+  for (int d = lane; d < dim; d += 64) s = __fmaf_rn(v[d], v[d], s);
+  for (int off = 1; off < 64; off <<= 1) s += __shfl_xor(s, off, 64);
+  return s;
+}
+
+__device__ inline float inv_sqrt_or_zero(float s) { return s > 0.f ? 1.f / sqrtf(s) : 0.f; }
+
+// Dot products of 16 rows (row0 ..) with G groups of 16 queries, one wave: acc[g][i] is
+// dot(q_hat[16 g + (lane & 15)], x[row0 + 4 (lane >> 4) + i]).  The X tile is operand A (lane l:
+// row l & 15, k = l >> 4), q_hat operand B (query l & 15, k = l >> 4); a lane loads d0 + 4 k .. + 3 and
+// feeds them to four MFMAs, so d is summed in the order d0 + 4 k + j over (d0, j, k) -- fixed.
+// Rows at or beyond `row_end` and dims at or beyond `dim` read as 0.
+template <int G, bool VEC>
+__device__ inline void score_tile(const float *__restrict__ X, int32_t dim, int64_t row0, int64_t row_end,
+                                  const float *__restrict__ qhat_tile, int lane, f32x4 (&acc)[G]) {
+  const int32_t dp = dim_pad_of(dim);
+  const int64_t row = row0 + (lane & 15);
+  const bool live = row < row_end;
+  const float *xr = X + (live ? row : 0) * (int64_t)dim;
+  const int k4 = 4 * (lane >> 4);
+  const float *qb = qhat_tile + (int64_t)(lane & 15) * dp + k4;
+#pragma unroll
+  for (int g = 0; g < G; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+  constexpr int kBatch = 8;  // X loads in flight per lane: 8 x 16 B
+  for (int db = 0; db < dp; db += 16 * kBatch) {
+    f32x4 xa[kBatch];
+#pragma unroll
+    for (int b = 0; b < kBatch; ++b) {
+      const int d = db + 16 * b + k4;
+      if (VEC) {
+        xa[b] = (live && d < dim) ? *reinterpret_cast<const f32x4 *>(xr + d) : f32x4{0.f, 0.f, 0.f, 0.f};
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xa[b][j] = (live && d + j < dim) ? xr[d + j] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < kBatch; ++b) {
+      const int d0 = db + 16 * b;
+      if (d0 >= dp) break;
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const f32x4 q4 = *reinterpret_cast<const f32x4 *>(qb + (int64_t)g * 16 * dp + d0);
+        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[b].x, q4.x, acc[g], 0, 0, 0);
+        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[b].y, q4.y, acc[g], 0, 0, 0);
+        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[b].z, q4.z, acc[g], 0, 0, 0);
+        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[b].w, q4.w, acc[g], 0, 0, 0);
+      }
+    }
+  }
+}
+
+}  // namespace

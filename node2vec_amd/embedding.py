@@ -331,6 +331,28 @@ class KeyedVectors:
         return linkpred.pair_features(self._device_vectors(), torch.from_numpy(ra), torch.from_numpy(rb),
                                       op).cpu().numpy()
 
+    def kmeans(self, k: int, metric: str = "cosine", restrict_vocab: Optional[int] = None, **kw):
+        """k-means of the vectors on the GPU (node2vec_amd.cluster.kmeans, whose other arguments pass through):
+        a KMeansResult whose labels[i] is the cluster of row i (token index2word[i]).  The default metric is
+        cosine (spherical k-means over the cached init_sims norms), as every similarity of this class is a
+        cosine; cluster.kmeans itself defaults to "euclidean" as scikit-learn does.  restrict_vocab: only the
+        first rows are clustered."""
+        from node2vec_amd import cluster
+
+        cluster._check_metric(metric)
+        n = len(self)
+        if restrict_vocab is not None:
+            if int(restrict_vocab) < 0:
+                raise ValueError("restrict_vocab must be >= 0")
+            n = min(n, int(restrict_vocab))
+        cluster._check_k(k, n)
+        X = self._device_vectors()[:n]
+        inv_norm = None
+        if metric == "cosine":
+            self.init_sims()
+            inv_norm = self._inv_norm[:n]
+        return cluster.kmeans(X, k, metric=metric, inv_norm=inv_norm, **kw)
+
     @classmethod
     def load_word2vec_format(cls, fname: str) -> "KeyedVectors":
         with open(fname) as f:
@@ -406,7 +428,40 @@ class _PairQueries:
         return pd.DataFrame({"src": src, "dst": dst, "vector": vectors})
 
 
-class Node2VecHIP(Node2VecBase, _PairQueries):
+class _ClusterQueries:
+    """cluster() of a fitted model: what Node2VecHIP and Node2VecSpark share."""
+
+    model = None
+    name_id = None
+    clusters = None
+    kmeans_result = None
+
+    def cluster(self, k: int, metric: str = "cosine", **kw) -> pd.DataFrame:
+        """["id" | "name", "cluster"]: the k-means cluster of every vocabulary vertex, in vocabulary order
+        (model.wv.kmeans, whose other arguments pass through; -1: a vertex whose vector holds NaN).  The default
+        metric is cosine, as in the rest of this class; node2vec_amd.cluster.kmeans defaults to "euclidean".
+        Names go through name_id as in most_similar(): a repeated id keeps its last name, an id that name_id does
+        not list is a KeyError.  The DataFrame is kept as self.clusters, the KMeansResult as self.kmeans_result."""
+        if self.model is None:
+            raise ValueError("Model is not available. Please run fit()")
+        wv = self.model.wv
+        ids = wv.ids if wv.ids is not None else np.array([int(t) for t in wv.index2word], dtype=np.int64)
+        names = None
+        if self.name_id is not None:
+            names = self.name_id.drop_duplicates("id", keep="last").set_index("id")["name"]
+            missing = ~pd.Index(ids).isin(names.index)
+            if missing.any():
+                raise KeyError(int(ids[missing][0]))
+        self.kmeans_result = wv.kmeans(k, metric=metric, **kw)
+        labels = self.kmeans_result.labels.cpu().numpy()
+        if names is None:
+            self.clusters = pd.DataFrame({"id": ids, "cluster": labels})
+        else:
+            self.clusters = pd.DataFrame({"name": names.reindex(ids).to_numpy(), "cluster": labels})
+        return self.clusters
+
+
+class Node2VecHIP(Node2VecBase, _PairQueries, _ClusterQueries):
     """Drop-in for Node2VecGensim (embedding.py:70-178) on one MI355X."""
 
     def __init__(
@@ -653,7 +708,7 @@ HIP_HS_PARAMS: Dict[str, Any] = {
 }
 
 
-class Node2VecSpark(Node2VecBase, _PairQueries):
+class Node2VecSpark(Node2VecBase, _PairQueries, _ClusterQueries):
     """Drop-in for the reference's Node2VecSpark (embedding.py:182-285) on one MI355X: skip-gram with
     hierarchical softmax, what Spark ML's Word2Vec trains (node2vec_amd/hs.py, csrc/n2v_hs.hip).
 

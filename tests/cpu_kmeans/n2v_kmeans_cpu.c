@@ -1,0 +1,135 @@
+/* CPU restatement of node2vec_amd/csrc/n2v_kmeans.hip: assignment, update and the fused step in the kernels'
+ * fixed orders.  Built by tests/kmeans_cases.py with -ffp-contract=off, so every line below is the fp32 or
+ * fp64 operation it spells.  This text is the contract; the kernels are held to its bits.
+ *
+ * dot(c, x):  acc = +0; for d0 = 0, 16, .. < round_up(dim, 16), j = 0..3, k = 0..3, d = d0 + 4 k + j:
+ *             acc = fmaf(x[d], c[d], acc), both read as 0 at d >= dim.
+ * sumsq(v):   s[l] = +0 for l in [0, 64); for d = l, l + 64, .. < dim: s[l] = fmaf(v[d], v[d], s[l]);
+ *             for off = 1, 2, 4, .. 32: every s[l] becomes s[l] + s[l ^ off] at once; the result is s[0].
+ * slabs:      S = min(2048, 512 MiB / (4 k dim)); slab_rows = round_up(max(1, ceil(n / S)), 64). */
+#include <math.h>
+#include <stdint.h>
+
+#define EUCLIDEAN 0
+#define COSINE 1
+
+float n2v_kmeans_cpu_dot(const float *c, const float *x, int32_t dim) {
+  const int32_t dp = (dim + 15) / 16 * 16;
+  float acc = 0.0f;
+  for (int32_t d0 = 0; d0 < dp; d0 += 16)
+    for (int j = 0; j < 4; ++j)
+      for (int k = 0; k < 4; ++k) {
+        const int32_t d = d0 + 4 * k + j;
+        acc = fmaf(d < dim ? x[d] : 0.0f, d < dim ? c[d] : 0.0f, acc);
+      }
+  return acc;
+}
+
+float n2v_kmeans_cpu_sumsq(const float *v, int32_t dim) {
+  float s[64], t[64];
+  for (int l = 0; l < 64; ++l) {
+    s[l] = 0.0f;
+    for (int32_t d = l; d < dim; d += 64) s[l] = fmaf(v[d], v[d], s[l]);
+  }
+  for (int off = 1; off < 64; off <<= 1) {
+    for (int l = 0; l < 64; ++l) t[l] = s[l] + s[l ^ off];
+    for (int l = 0; l < 64; ++l) s[l] = t[l];
+  }
+  return s[0];
+}
+
+static float inv_sqrt_or_zero(float s) { return s > 0.0f ? 1.0f / sqrtf(s) : 0.0f; }
+
+void n2v_kmeans_cpu_inv_norms(const float *X, int64_t n, int32_t dim, float *out) {
+  for (int64_t r = 0; r < n; ++r) out[r] = inv_sqrt_or_zero(n2v_kmeans_cpu_sumsq(X + r * dim, dim));
+}
+
+int64_t n2v_kmeans_cpu_slab_rows(int64_t n, int32_t dim, int32_t k) {
+  int64_t most = (512ll << 20) / ((int64_t)k * dim * 4);
+  if (most > 2048) most = 2048;
+  int64_t share = (n + most - 1) / most;
+  if (share < 1) share = 1;
+  return (share + 63) / 64 * 64;
+}
+
+/* label: c ascending from best = +inf, label = -1, taken when t < best (strictly); dist: NULL or [n] */
+void n2v_kmeans_cpu_assign(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *C, int32_t k,
+                           int32_t metric, int32_t *labels, float *dist) {
+  float cn[1024];
+  for (int32_t c = 0; c < k; ++c) cn[c] = n2v_kmeans_cpu_sumsq(C + (int64_t)c * dim, dim);
+  for (int64_t r = 0; r < n; ++r) {
+    const float *x = X + r * dim;
+    float best = INFINITY;
+    int32_t label = -1;
+    for (int32_t c = 0; c < k; ++c) {
+      const float dot = n2v_kmeans_cpu_dot(C + (int64_t)c * dim, x, dim);
+      const float t = metric == COSINE ? -dot : fmaf(-2.0f, dot, cn[c]);
+      if (t < best) best = t, label = c;
+    }
+    labels[r] = label;
+    if (!dist) continue;
+    if (label < 0) {
+      dist[r] = NAN;
+    } else if (metric == COSINE) {
+      const float dot_best = -best;
+      const float scaled = dot_best * inv_norm[r];
+      dist[r] = 1.0f - scaled;
+    } else {
+      const float sum = best + n2v_kmeans_cpu_sumsq(x, dim);
+      dist[r] = fmaxf(sum, 0.0f);
+    }
+  }
+}
+
+/* part: scratch of k * dim floats, sum: scratch of k * dim doubles (both supplied by the caller) */
+void n2v_kmeans_cpu_update(const float *X, const float *inv_norm, int64_t n, int32_t dim, const int32_t *labels,
+                           int32_t k, int32_t metric, const float *prev, float *out, int64_t *counts, float *part,
+                           double *sum) {
+  const int64_t slab = n2v_kmeans_cpu_slab_rows(n, dim, k);
+  const int64_t kd = (int64_t)k * dim;
+  for (int64_t i = 0; i < kd; ++i) sum[i] = 0.0;
+  for (int32_t c = 0; c < k; ++c) counts[c] = 0;
+  for (int64_t lo = 0; lo < n; lo += slab) {
+    const int64_t hi = lo + slab < n ? lo + slab : n;
+    for (int64_t i = 0; i < kd; ++i) part[i] = 0.0f;
+    for (int64_t r = lo; r < hi; ++r) {
+      const int32_t c = labels[r];
+      if (c < 0 || c >= k) continue; /* not a label: as -1 */
+      counts[c] += 1;
+      for (int32_t d = 0; d < dim; ++d) {
+        float v = X[r * dim + d];
+        if (metric == COSINE) v = v * inv_norm[r];
+        part[(int64_t)c * dim + d] = part[(int64_t)c * dim + d] + v;
+      }
+    }
+    for (int64_t i = 0; i < kd; ++i) sum[i] = sum[i] + (double)part[i];
+  }
+  float f[1024];
+  for (int32_t c = 0; c < k; ++c) {
+    const double *s = sum + (int64_t)c * dim;
+    const float *p = prev + (int64_t)c * dim;
+    float *o = out + (int64_t)c * dim;
+    if (metric == COSINE) {
+      for (int32_t d = 0; d < dim; ++d) f[d] = (float)s[d];
+      const float inv = inv_sqrt_or_zero(n2v_kmeans_cpu_sumsq(f, dim));
+      const int keep = counts[c] == 0 || !(inv > 0.0f);
+      for (int32_t d = 0; d < dim; ++d) o[d] = keep ? p[d] : f[d] * inv;
+    } else {
+      for (int32_t d = 0; d < dim; ++d) o[d] = counts[c] ? (float)(s[d] / (double)counts[c]) : p[d];
+    }
+  }
+}
+
+/* assign against C, then update with C as the previous centroids; stats = {labels changed, rows left at -1} */
+void n2v_kmeans_cpu_step(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *C, int32_t k,
+                         int32_t metric, int32_t *labels_inout, float *dist, float *out, int64_t *counts,
+                         int64_t *stats, int32_t *labels_scratch, float *part, double *sum) {
+  n2v_kmeans_cpu_assign(X, inv_norm, n, dim, C, k, metric, labels_scratch, dist);
+  stats[0] = stats[1] = 0;
+  for (int64_t r = 0; r < n; ++r) {
+    stats[0] += labels_inout[r] != labels_scratch[r];
+    stats[1] += labels_scratch[r] < 0;
+    labels_inout[r] = labels_scratch[r];
+  }
+  n2v_kmeans_cpu_update(X, inv_norm, n, dim, labels_inout, k, metric, C, out, counts, part, sum);
+}
