@@ -18,7 +18,7 @@
 // (lane l owns elements l*VEC .., then the butterfly over lane distances 1 .. 32) where BLAS sdot
 // leaves the order open; FMAs where the skip-gram kernel spells them; the seeded initialisation.
 //
-// Design: one wave64 per sentence, sentence preparation as sgns_kernel.  Every row of a position is
+// Design: one wave64 per sentence, sentence preparation a copy of sgns_kernel's.  Every row of a position is
 // known before any arithmetic -- up to 2 * window context rows and 1 + negative target rows -- and the
 // target rows do not depend on neu1, so the first kTG target rows are requested BEFORE the context
 // rows are summed: one round trip to memory covers both.  Context rows are summed in groups of kCG
@@ -27,12 +27,12 @@
 // read back after that one's store.  The negative draws of 64 / negative positions are made at once,
 // lane-parallel, so the dependent probes of a bisect are paid once per ~12 positions.  The second
 // pass over the context rows reads each row again and stores row + work (read-modify-write, the
-// agent-scope accesses of n2v_sgns_rows.h at dim <= 128); rows below hub_rows (hogwild only) take
+// agent-scope accesses of n2v_w2v_core.h at dim <= 128); rows below hub_rows (hogwild only) take
 // atomic adds of this wave's contribution instead.
 #include <cstdlib>
 
 #include "n2v_common.h"
-#include "n2v_sgns_rows.h"
+#include "n2v_w2v_core.h"
 
 namespace n2v {
 namespace cbow {
@@ -71,10 +71,7 @@ __global__ __launch_bounds__(kWaves * 64) void cbow_kernel(
   int32_t *red = sent + sent_cap;
   int32_t *neg = red + sent_cap;
   for (int i = threadIdx.x; i < kExpTable; i += blockDim.x) exp_lds[i] = exp_table_g[i];
-  const int bis_iters = 64 - __clzll((long long)P.n_vocab);
-  if (!P.cum_index)
-    for (int b = threadIdx.x; b <= kBuckets; b += blockDim.x)
-      bucket[b] = bisect_left_u32(cum_table, P.n_vocab, (uint32_t)b << 21, bis_iters);
+  if (!P.cum_index) bucket_table_build(bucket, cum_table, P.n_vocab);
   __syncthreads();
 
   const int dim = P.dim, window = P.window, K = P.negative;
@@ -96,31 +93,27 @@ __global__ __launch_bounds__(kWaves * 64) void cbow_kernel(
   unsigned int *row_counter = reinterpret_cast<unsigned int *>(pairs_out + 1);
   int64_t rr = (int64_t)blockIdx.x * waves_per_block + wave_in_block;
   for (;;) {
-    if (dynamic) {
-      unsigned int t = 0;
-      if (lane == 0) t = atomicAdd(row_counter, 1u);
-      rr = (int64_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)t);
-    }
+    if (dynamic) rr = claim_row(row_counter, lane);
     if (rr >= n_walks) break;
     const int64_t r = readfirstlane_i64(rr);
     if (!dynamic) rr += n_waves;
     const uint64_t hs = sentence_stream(P.seed, (uint64_t)(P.sentence_base + r));
     if (P.row_alpha) alpha = P.row_alpha[r];
-    // ---- sentence preparation: that of sgns_kernel ----
+    // ---- sentence preparation: a copy of sgns_kernel's (shared as a function it changes the assembly) ----
     int nf = 0;
     for (int base = 0; base < walk_len; base += 64) {
       const int t = base + lane;
       int32_t tok = t < walk_len ? walks[r * walk_len + t] : -1;
       bool keep = tok >= 0 && (int64_t)tok < P.n_vocab;
       if (keep && sample_int) {
-        uint32_t rnd = (uint32_t)(sgns_draw(hs, 2ULL * (uint64_t)t) >> 32);
+        uint32_t rnd = (uint32_t)(sentence_draw(hs, 2ULL * (uint64_t)t) >> 32);
         keep = !(sample_int[tok] < rnd);
       }
       const uint64_t mask = ballot64(keep);
       const int pos = nf + __popcll(mask & ((1ull << lane) - 1ull));
       if (keep) {
         sent[pos] = tok;
-        red[pos] = (int32_t)((uint32_t)(sgns_draw(hs, 2ULL * (uint64_t)t + 1ULL) >> 32) % (uint32_t)window);
+        red[pos] = (int32_t)((uint32_t)(sentence_draw(hs, 2ULL * (uint64_t)t + 1ULL) >> 32) % (uint32_t)window);
       }
       nf += __popcll(mask);
     }
@@ -135,7 +128,7 @@ __global__ __launch_bounds__(kWaves * 64) void cbow_kernel(
         const int jj = lane / K, d = lane - jj * K;
         if (jj < ppb && i + jj < nf) {
           const uint64_t idx = 2ULL * (uint64_t)walk_len + (uint64_t)(i + jj) * (uint64_t)K + (uint64_t)d;
-          const uint32_t x = (uint32_t)((sgns_draw(hs, idx) >> 16) % (uint64_t)domain);
+          const uint32_t x = (uint32_t)((sentence_draw(hs, idx) >> 16) % (uint64_t)domain);
           int blo, bhi;
           if (P.cum_index) {
             const uint32_t bk = x >> (31 - P.cum_index_bits);
@@ -297,9 +290,7 @@ __global__ __launch_bounds__(kWaves * 64) void cbow_kernel(
           if (cw[e] < 0) continue;
           float *p = syn0 + (int64_t)cw[e] * dim;
           if (cw[e] < hub_rows) {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v)
-              if (lane * VEC + v < dim) unsafeAtomicAdd(p + lane * VEC + v, work.v[v]);
+            add_row<VEC>(p, dim, lane, work);
             continue;
           }
           bool dup = false;
@@ -325,9 +316,7 @@ static int train_impl(const int32_t *walks, int64_t n_walks, int32_t walk_len, f
                       int64_t *dry_waves) {
   if (!P) return N2V_EINVAL;
   if (!dry_waves && (!walks || !syn0 || !syn1neg || !cum_table || !exp_table)) return N2V_EINVAL;
-  if (n_walks < 0 || walk_len < 1 || walk_len > N2V_SGNS_MAX_SENTENCE) return N2V_EINVAL;
-  if (P->n_vocab < 1 || P->n_vocab >= (1ll << 31) || P->dim < 1 || P->dim > 1024 || P->window < 1 ||
-      P->window > 32 || P->negative < 1 || P->negative > 32)
+  if (!check_common(P->n_vocab, P->dim, P->window, n_walks, walk_len) || P->negative < 1 || P->negative > 32)
     return N2V_EINVAL;
   if (P->batched != 0 || P->window_cache != 0) return N2V_EINVAL;  // skip-gram variants
   if (cbow_mean != 0 && cbow_mean != 1) return N2V_EINVAL;
@@ -335,53 +324,22 @@ static int train_impl(const int32_t *walks, int64_t n_walks, int32_t walk_len, f
   if (P->cum_index && (P->cum_index_bits < 1 || P->cum_index_bits > 30)) return N2V_EINVAL;
   if (dry_waves) *dry_waves = 0;
   if (n_walks == 0) return N2V_OK;
-  int V = 1;
-  while (64 * V < P->dim) V *= 2;
-  const int sent_cap = (walk_len + 3) & ~3;
+  const int V = vec_of(P->dim);
+  const int sent_cap = sent_cap_of(walk_len);
   const size_t lds = kExpTable * sizeof(float) + (P->cum_index ? 0 : (kBuckets + 1 + 3) * sizeof(int32_t)) +
                      (size_t)kWaves * (size_t)(2 * sent_cap + kNegSlots) * 4;
-  // hogwild concurrency: one wave per 32 vocabulary rows, up to the whole chip (the skip-gram rule)
-  int64_t waves = P->n_vocab / 32;
-  if (waves < 1) waves = 1;
-  if (waves > n_walks) waves = n_walks;
-  if (P->max_waves > 0 && waves > P->max_waves) waves = P->max_waves;
-  int64_t blocks = (waves + kWaves - 1) / kWaves;
-  dim3 block(kWaves * 64);
-  if (waves < kWaves) block = dim3((unsigned)waves * 64);
-  if (P->deterministic) {
-    blocks = 1;
-    block = dim3(64);
-  }
-  hipStream_t st = (hipStream_t)stream;
-  // pairs_out[1] is the kernel's row counter: start it at zero on the same stream
-  if (!dry_waves && pairs_out && hipMemsetAsync(pairs_out + 1, 0, sizeof(unsigned long long), st) != hipSuccess)
-    return N2V_ELAUNCH;
-#define N2V_CBOW_LAUNCH(VV)                                                                             \
-  do {                                                                                                  \
-    const void *fn = (const void *)cbow_kernel<VV>;                                                     \
-    if (!P->deterministic) {                                                                            \
-      const int64_t cap = resident_blocks(fn, (int)block.x, lds);                                       \
-      if (blocks > cap) blocks = cap;                                                                   \
-    }                                                                                                   \
-    if (dry_waves) {                                                                                    \
-      *dry_waves = blocks * (int64_t)(block.x / 64);                                                    \
-      break;                                                                                            \
-    }                                                                                                   \
-    hipLaunchKernelGGL((cbow_kernel<VV>), dim3((unsigned)blocks), block, lds, st, walks, n_walks,       \
-                       walk_len, syn0, syn1neg, cum_table, sample_int, exp_table, *P, cbow_mean,        \
-                       pairs_out, sent_cap);                                                            \
-  } while (0)
+  const LaunchGeometry geo = hogwild_geometry(P->n_vocab, n_walks, P->max_waves, P->deterministic, kWaves);
+  auto launch = [&](auto kernel) {
+    return launch_trainer(kernel, geo, lds, P->deterministic, pairs_out, stream, dry_waves, walks, n_walks, walk_len,
+                          syn0, syn1neg, cum_table, sample_int, exp_table, *P, cbow_mean, pairs_out, sent_cap);
+  };
   switch (V) {
-    case 1: N2V_CBOW_LAUNCH(1); break;
-    case 2: N2V_CBOW_LAUNCH(2); break;
-    case 4: N2V_CBOW_LAUNCH(4); break;
-    case 8: N2V_CBOW_LAUNCH(8); break;
-    default: N2V_CBOW_LAUNCH(16); break;
+    case 1: return launch(cbow_kernel<1>);
+    case 2: return launch(cbow_kernel<2>);
+    case 4: return launch(cbow_kernel<4>);
+    case 8: return launch(cbow_kernel<8>);
+    default: return launch(cbow_kernel<16>);
   }
-#undef N2V_CBOW_LAUNCH
-  if (dry_waves) return N2V_OK;
-  N2V_HIP_CHECK(hipGetLastError());
-  return N2V_OK;
 }
 
 }  // namespace cbow

@@ -9,7 +9,7 @@
 // chain of dependent parent-pointer loads.
 //
 // hs_kernel: one wave64 per sentence, lane l owns VEC elements of a row, dot products closed by
-// the same DPP tree as the SGNS kernel.  All contexts of one centre position walk the same path:
+// the DPP tree of wave_dot (n2v_w2v_core.h).  All contexts of one centre position walk the same path:
 // the top `cache_rows` path rows are read into LDS once per position, updated across its
 // contexts, and written back once (exact: the updates are applied in the sequential order).
 // Within one pair every node's dot product depends only on syn0[context] and that node's row,
@@ -22,127 +22,16 @@
 #include <vector>
 
 #include "n2v_common.h"
+#include "n2v_w2v_core.h"
 
 namespace n2v {
 namespace hs {
 
 constexpr int kWaves = 4;        // waves per block
-constexpr int kExpTable = 1000;  // EXP_TABLE_SIZE
 constexpr int kMaxCode = 64;     // code bits per word (one uint64)
 
-__host__ __device__ inline uint64_t sentence_stream(uint64_t seed, uint64_t sentence_id) {
-  return mix64(seed ^ mix64(sentence_id + 0xA0761D6478BD642FULL));
-}
-__host__ __device__ inline uint64_t hs_draw(uint64_t hs, uint64_t idx) {
-  return mix64(hs + (idx + 1ULL) * 0xE7037ED1A0B428DBULL);
-}
-
-template <int VEC>
-struct Row {
-  float v[VEC];
-};
-
-// Agent-scope accesses for rows of up to 128 floats (the XCDs' L2s are not coherent; the same
-// rule and measurements as row_ld1 in n2v_sgns_rows.h).  Wider rows stay plain.
-__device__ __forceinline__ float ld1(const float *p) {
-  return __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned int *>(p), __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT));
-}
-__device__ __forceinline__ void st1(float *p, float x) {
-  __hip_atomic_store(reinterpret_cast<unsigned int *>(p), __float_as_uint(x), __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <int VEC>
-__device__ __forceinline__ void load_row(const float *base, int dim, int lane, bool full, Row<VEC> &r) {
-  if (full) {
-    if constexpr (VEC == 1) {
-      r.v[0] = ld1(base + lane);
-    } else if constexpr (VEC == 2) {
-      const unsigned long long u = __hip_atomic_load(reinterpret_cast<const unsigned long long *>(base + lane * 2),
-                                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      r.v[0] = __uint_as_float((unsigned int)u);
-      r.v[1] = __uint_as_float((unsigned int)(u >> 32));
-    } else {
-#pragma unroll
-      for (int q = 0; q < VEC / 4; ++q) {
-        float4 t = *reinterpret_cast<const float4 *>(base + lane * VEC + q * 4);
-        r.v[4 * q + 0] = t.x;
-        r.v[4 * q + 1] = t.y;
-        r.v[4 * q + 2] = t.z;
-        r.v[4 * q + 3] = t.w;
-      }
-    }
-  } else {
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      const int e = lane * VEC + v;
-      r.v[v] = e < dim ? (VEC <= 2 ? ld1(base + e) : base[e]) : 0.0f;
-    }
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void store_row(float *base, int dim, int lane, bool full, const Row<VEC> &r) {
-  if (full) {
-    if constexpr (VEC == 1) {
-      st1(base + lane, r.v[0]);
-    } else if constexpr (VEC == 2) {
-      const unsigned long long u = (unsigned long long)__float_as_uint(r.v[0]) |
-                                   ((unsigned long long)__float_as_uint(r.v[1]) << 32);
-      __hip_atomic_store(reinterpret_cast<unsigned long long *>(base + lane * 2), u, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-#pragma unroll
-      for (int q = 0; q < VEC / 4; ++q)
-        *reinterpret_cast<float4 *>(base + lane * VEC + q * 4) =
-            make_float4(r.v[4 * q], r.v[4 * q + 1], r.v[4 * q + 2], r.v[4 * q + 3]);
-    }
-  } else {
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-      const int e = lane * VEC + v;
-      if (e < dim) {
-        if (VEC <= 2)
-          st1(base + e, r.v[v]);
-        else
-          base[e] = r.v[v];
-      }
-    }
-  }
-}
-
-// no-return f32 atomic add of a lane's elements (global_atomic_add_f32)
-template <int VEC>
-__device__ __forceinline__ void add_row(float *base, int dim, int lane, const Row<VEC> &d) {
-#pragma unroll
-  for (int v = 0; v < VEC; ++v)
-    if (lane * VEC + v < dim) unsafeAtomicAdd(base + lane * VEC + v, d.v[v]);
-}
-
-template <int kCtrl>
-__device__ __forceinline__ float dpp_move(float x) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), kCtrl, 0xF, 0xF, true));
-}
-
-// The SGNS kernel's wave dot product (n2v_sgns.hip wave_dot): per-lane fmaf chain, then lane
-// distances 1, 2, 4, 8 by DPP and the four row sums as (R0 + R1) + (R2 + R3).  Independent calls
-// on different rows are interleaved by the compiler (several reductions per DPP chain).
-template <int VEC>
-__device__ __forceinline__ float wave_dot(const Row<VEC> &a, const Row<VEC> &b) {
-  float acc = 0.0f;
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) acc = __fmaf_rn(a.v[v], b.v[v], acc);
-  acc = acc + dpp_move<0xB1>(acc);
-  acc = acc + dpp_move<0x4E>(acc);
-  acc = acc + dpp_move<0x141>(acc);
-  acc = acc + dpp_move<0x140>(acc);
-  const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 0));
-  const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 16));
-  const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 32));
-  const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 48));
-  return (r0 + r1) + (r2 + r3);
-}
+// ragged rows of more than 128 floats are accessed plainly here (load_row in n2v_w2v_core.h)
+constexpr bool kWideRaggedPlain = true;
 
 // path nodes trained together per group: 16 floats of rows per lane, and at least two nodes, so that
 // the loads of a group are issued together.  (syn1 is not restrict: the store of a group's last
@@ -180,20 +69,16 @@ __global__ __launch_bounds__(kWaves * 64) void hs_kernel(
   // hogwild only: syn1 rows [hot_lo, V - 1) -- the top hot_nodes inner nodes -- take atomic adds
   const int64_t hot_lo = hogwild ? (V - 1) - (int64_t)P.hot_nodes : (int64_t)1 << 62;
   float alpha = P.alpha;
-  const int waves_per_block = blockDim.x >> 6;
   unsigned long long pairs = 0;
-  const bool dynamic = pairs_out != nullptr;
+  auto lds_row = [&](float *base, int slot) { return base + slot * row_floats + lane * VEC; };
+
+  const int waves_per_block = blockDim.x >> 6;
+  const bool dynamic = pairs_out != nullptr && n_walks < 0xfffffff0ll;
   unsigned int *row_counter = reinterpret_cast<unsigned int *>(pairs_out + 1);
   int64_t rr = (int64_t)blockIdx.x * waves_per_block + wave_in_block;
   const int64_t n_waves = (int64_t)gridDim.x * waves_per_block;
-  auto lds_row = [&](float *base, int slot) { return base + slot * row_floats + lane * VEC; };
-
   for (;;) {
-    if (dynamic) {
-      unsigned int t = 0;
-      if (lane == 0) t = atomicAdd(row_counter, 1u);
-      rr = (int64_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)t);
-    }
+    if (dynamic) rr = claim_row(row_counter, lane);
     if (rr >= n_walks) break;
     const int64_t r = readfirstlane_i64(rr);
     if (!dynamic) rr += n_waves;
@@ -209,7 +94,7 @@ __global__ __launch_bounds__(kWaves * 64) void hs_kernel(
       const int pos = nf + __popcll(mask & ((1ull << lane) - 1ull));
       if (keep) {
         sent[pos] = tok;
-        red[pos] = (int32_t)((uint32_t)(hs_draw(hsd, 2ULL * (uint64_t)t + 1ULL) >> 32) % (uint32_t)window);
+        red[pos] = (int32_t)((uint32_t)(sentence_draw(hsd, 2ULL * (uint64_t)t + 1ULL) >> 32) % (uint32_t)window);
       }
       nf += __popcll(mask);
     }
@@ -231,7 +116,7 @@ __global__ __launch_bounds__(kWaves * 64) void hs_kernel(
       for (int d = 0; d < nc; ++d) {
         const int32_t p = __builtin_amdgcn_readlane(my_point, d);
         Row<VEC> t;
-        load_row<VEC>(syn1 + (int64_t)p * dim, dim, lane, full, t);
+        load_row<VEC, kWideRaggedPlain>(syn1 + (int64_t)p * dim, dim, lane, full, t);
         float *q = lds_row(cache, d);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) q[v] = t.v[v];
@@ -249,7 +134,7 @@ __global__ __launch_bounds__(kWaves * 64) void hs_kernel(
         // repeated inside the window sees its own update
         float *p0 = syn0 + (int64_t)__builtin_amdgcn_readfirstlane(sent[j]) * dim;
         Row<VEC> x, neu;
-        load_row<VEC>(p0, dim, lane, full, x);
+        load_row<VEC, kWideRaggedPlain>(p0, dim, lane, full, x);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) neu.v[v] = 0.0f;
         for (int d0 = 0; d0 < len; d0 += NB) {
@@ -266,7 +151,7 @@ __global__ __launch_bounds__(kWaves * 64) void hs_kernel(
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) rows[k].v[v] = q[v];
               } else {
-                load_row<VEC>(syn1 + (int64_t)pt[k] * dim, dim, lane, full, rows[k]);
+                load_row<VEC, kWideRaggedPlain>(syn1 + (int64_t)pt[k] * dim, dim, lane, full, rows[k]);
               }
             }
           }
@@ -293,13 +178,13 @@ __global__ __launch_bounds__(kWaves * 64) void hs_kernel(
             } else if ((int64_t)pt[k] >= hot_lo) {
               add_row<VEC>(syn1 + (int64_t)pt[k] * dim, dim, lane, delta);
             } else {
-              store_row<VEC>(syn1 + (int64_t)pt[k] * dim, dim, lane, full, rows[k]);
+              store_row<VEC, kWideRaggedPlain>(syn1 + (int64_t)pt[k] * dim, dim, lane, full, rows[k]);
             }
           }
         }
 #pragma unroll
         for (int v = 0; v < VEC; ++v) x.v[v] = x.v[v] + neu.v[v];
-        store_row<VEC>(p0, dim, lane, full, x);
+        store_row<VEC, kWideRaggedPlain>(p0, dim, lane, full, x);
       }
       // ---- write the cached path rows back, once per position ----
       for (int d = 0; d < nc; ++d) {
@@ -315,7 +200,7 @@ __global__ __launch_bounds__(kWaves * 64) void hs_kernel(
           for (int v = 0; v < VEC; ++v) t.v[v] = t.v[v] - q0[v];
           add_row<VEC>(dst, dim, lane, t);
         } else {
-          store_row<VEC>(dst, dim, lane, full, t);
+          store_row<VEC, kWideRaggedPlain>(dst, dim, lane, full, t);
         }
       }
       __builtin_amdgcn_wave_barrier();
@@ -403,10 +288,7 @@ int hs_train_impl(const int32_t *walks, int64_t n_walks, int32_t walk_len, float
                   const n2v_hs_params *P, unsigned long long *pairs_out, void *stream, int64_t *dry_waves) {
   if (!P) return N2V_EINVAL;
   if (!dry_waves && (!walks || !syn0 || !syn1 || !path_off || !points || !codes || !exp_table)) return N2V_EINVAL;
-  if (n_walks < 0 || walk_len < 1 || walk_len > N2V_SGNS_MAX_SENTENCE) return N2V_EINVAL;
-  if (P->n_vocab < 1 || P->n_vocab >= (1ll << 31) || P->dim < 1 || P->dim > 1024 || P->window < 1 ||
-      P->window > 32)
-    return N2V_EINVAL;
+  if (!n2v::check_common(P->n_vocab, P->dim, P->window, n_walks, walk_len)) return N2V_EINVAL;
   if (P->deterministic != 0 && P->deterministic != 1) return N2V_EINVAL;
   if (P->path_cache != 0 && P->path_cache != 1) return N2V_EINVAL;
   // hot_nodes > 0 (atomic adds on the top inner nodes) measured slower and worse than plain stores, and
@@ -416,55 +298,23 @@ int hs_train_impl(const int32_t *walks, int64_t n_walks, int32_t walk_len, float
   if (n_walks == 0) return N2V_OK;
   using namespace n2v;
   using namespace n2v::hs;
-  int vec = 1;
-  while (64 * vec < P->dim) vec *= 2;
+  const int vec = vec_of(P->dim);
   const int cache_rows = hs_cache_rows(P, vec);
-  const int sent_cap = (walk_len + 3) & ~3;
+  const int sent_cap = sent_cap_of(walk_len);
   const size_t per_wave = (size_t)2 * sent_cap + (size_t)cache_rows * 64 * vec * (P->deterministic ? 1 : 2);
   const size_t lds = kExpTable * sizeof(float) + (size_t)(P->deterministic ? 1 : kWaves) * per_wave * 4;
-  // hogwild concurrency: one wave per 32 vocabulary rows, up to the whole chip (the SGNS rule)
-  int64_t waves = P->n_vocab / 32;
-  if (waves < 1) waves = 1;
-  if (waves > n_walks) waves = n_walks;
-  if (P->max_waves > 0 && waves > P->max_waves) waves = P->max_waves;
-  int64_t blocks = (waves + kWaves - 1) / kWaves;
-  dim3 block(kWaves * 64);
-  if (waves < kWaves) block = dim3((unsigned)waves * 64);
-  if (P->deterministic) {
-    blocks = 1;
-    block = dim3(64);
-  }
-  hipStream_t st = (hipStream_t)stream;
-  if (!dry_waves && pairs_out && hipMemsetAsync(pairs_out + 1, 0, sizeof(unsigned long long), st) != hipSuccess)
-    return N2V_ELAUNCH;
-#define N2V_HS_LAUNCH(VV)                                                                              \
-  do {                                                                                                 \
-    const void *fn = (const void *)hs_kernel<VV>;                                                      \
-    if (lds > 64 * 1024 &&                                                                             \
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)   \
-      return N2V_ELAUNCH;                                                                              \
-    if (!P->deterministic) {                                                                           \
-      const int64_t cap = resident_blocks(fn, (int)block.x, lds);                                      \
-      if (blocks > cap) blocks = cap;                                                                  \
-    }                                                                                                  \
-    if (dry_waves) {                                                                                   \
-      *dry_waves = blocks * (int64_t)(block.x / 64);                                                   \
-      break;                                                                                           \
-    }                                                                                                  \
-    hipLaunchKernelGGL((hs_kernel<VV>), dim3((unsigned)blocks), block, lds, st, walks, n_walks, walk_len, \
-                       syn0, syn1, path_off, points, codes, exp_table, *P, pairs_out, sent_cap, cache_rows); \
-  } while (0)
+  const LaunchGeometry geo = hogwild_geometry(P->n_vocab, n_walks, P->max_waves, P->deterministic, kWaves);
+  auto launch = [&](auto kernel) {
+    return launch_trainer(kernel, geo, lds, P->deterministic, pairs_out, stream, dry_waves, walks, n_walks, walk_len,
+                          syn0, syn1, path_off, points, codes, exp_table, *P, pairs_out, sent_cap, cache_rows);
+  };
   switch (vec) {
-    case 1: N2V_HS_LAUNCH(1); break;
-    case 2: N2V_HS_LAUNCH(2); break;
-    case 4: N2V_HS_LAUNCH(4); break;
-    case 8: N2V_HS_LAUNCH(8); break;
-    default: N2V_HS_LAUNCH(16); break;
+    case 1: return launch(hs_kernel<1>);
+    case 2: return launch(hs_kernel<2>);
+    case 4: return launch(hs_kernel<4>);
+    case 8: return launch(hs_kernel<8>);
+    default: return launch(hs_kernel<16>);
   }
-#undef N2V_HS_LAUNCH
-  if (dry_waves) return N2V_OK;
-  N2V_HIP_CHECK(hipGetLastError());
-  return N2V_OK;
 }
 }  // namespace
 

@@ -16,7 +16,7 @@
 #include <cstdlib>
 
 #include "n2v_common.h"
-#include "n2v_sgns_rows.h"
+#include "n2v_w2v_core.h"
 
 namespace n2v {
 
@@ -58,12 +58,7 @@ __global__ __launch_bounds__(kSgnsWaves * 64, (kRingRows ? (VEC <= 2 ? 4 : 1) : 
   int32_t *neg = red + sent_cap;
   float *ring = reinterpret_cast<float *>(sent + ints_per_wave);  // [ring_rows][64 * VEC]
   for (int i = threadIdx.x; i < kExpTable; i += blockDim.x) exp_lds[i] = exp_table_g[i];
-  const int bis_iters = 64 - __clzll((long long)P.n_vocab);
-  // bucket[b] = bisect_left(cum_table, b << 21): a draw r lies in bucket r >> 21 and its
-  // bisect_left is confined to [bucket[b], bucket[b+1]] -- same index, half the probes
-  if (!P.cum_index)
-    for (int b = threadIdx.x; b <= kBuckets; b += blockDim.x)
-      bucket[b] = bisect_left_u32(cum_table, P.n_vocab, (uint32_t)b << 21, bis_iters);
+  if (!P.cum_index) bucket_table_build(bucket, cum_table, P.n_vocab);
   __syncthreads();
 
   const int dim = P.dim, window = P.window, K = P.negative;
@@ -85,11 +80,7 @@ __global__ __launch_bounds__(kSgnsWaves * 64, (kRingRows ? (VEC <= 2 ? 4 : 1) : 
   unsigned int *row_counter = reinterpret_cast<unsigned int *>(pairs_out + 1);
   int64_t rr = (int64_t)blockIdx.x * waves_per_block + wave_in_block;
   for (;;) {
-    if (dynamic) {
-      unsigned int t = 0;
-      if (lane == 0) t = atomicAdd(row_counter, 1u);
-      rr = (int64_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)t);
-    }
+    if (dynamic) rr = claim_row(row_counter, lane);
     if (rr >= n_walks) break;
     const int64_t r = readfirstlane_i64(rr);
     if (!dynamic) rr += n_waves;
@@ -102,14 +93,14 @@ __global__ __launch_bounds__(kSgnsWaves * 64, (kRingRows ? (VEC <= 2 ? 4 : 1) : 
       int32_t tok = t < walk_len ? walks[r * walk_len + t] : -1;
       bool keep = tok >= 0 && (int64_t)tok < P.n_vocab;
       if (keep && sample_int) {
-        uint32_t rnd = (uint32_t)(sgns_draw(hs, 2ULL * (uint64_t)t) >> 32);
+        uint32_t rnd = (uint32_t)(sentence_draw(hs, 2ULL * (uint64_t)t) >> 32);
         keep = !(sample_int[tok] < rnd);
       }
       const uint64_t mask = ballot64(keep);
       const int pos = nf + __popcll(mask & ((1ull << lane) - 1ull));
       if (keep) {
         sent[pos] = tok;
-        red[pos] = (int32_t)((uint32_t)(sgns_draw(hs, 2ULL * (uint64_t)t + 1ULL) >> 32) %
+        red[pos] = (int32_t)((uint32_t)(sentence_draw(hs, 2ULL * (uint64_t)t + 1ULL) >> 32) %
                              (uint32_t)window);
       }
       nf += __popcll(mask);
@@ -217,7 +208,7 @@ __global__ __launch_bounds__(kSgnsWaves * 64, (kRingRows ? (VEC <= 2 ? 4 : 1) : 
         const uint64_t idx = 2ULL * (uint64_t)walk_len +
                              ((uint64_t)i * 2ULL * (uint64_t)window + (uint64_t)rel) *
                                  (uint64_t)K + (uint64_t)d;
-        const uint32_t x = (uint32_t)((sgns_draw(hs, idx) >> 16) % (uint64_t)domain);
+        const uint32_t x = (uint32_t)((sentence_draw(hs, idx) >> 16) % (uint64_t)domain);
         // bisect_left(cum_table, x) is confined to the bucket of x: [index[b], index[b + 1]] with
         // b = x >> shift -- through the caller's fine index in HBM (n2v_cum_index_build: with
         // 10^8 words a draw costs one index sector + one table sector instead of ~17 dependent
@@ -482,6 +473,13 @@ extern "C" int n2v_sgns_batched_launch(const int32_t *walks, int64_t n_walks, in
                                        const n2v_sgns_params *P, unsigned long long *pairs_out,
                                        void *stream);
 
+// the instance with a window cache of `ring` rows (0: none)
+template <int VEC, typename Launch>
+static int launch_ring(int ring, Launch launch) {
+  if (ring == 0) return launch(n2v::sgns_kernel<VEC, 1, 0>);
+  return ring == 12 ? launch(n2v::sgns_kernel<VEC, 1, 12>) : launch(n2v::sgns_kernel<VEC, 1, 16>);
+}
+
 // n2v_sgns_train, or (dry_waves != NULL) only its launch geometry: the waves it would keep in flight
 static int sgns_train_impl(const int32_t *walks, int64_t n_walks, int32_t walk_len,
                            float *syn0, float *syn1neg, const uint32_t *cum_table,
@@ -490,9 +488,7 @@ static int sgns_train_impl(const int32_t *walks, int64_t n_walks, int32_t walk_l
                            void *stream, int64_t *dry_waves) {
   if (!P) return N2V_EINVAL;
   if (!dry_waves && (!walks || !syn0 || !syn1neg || !cum_table || !exp_table)) return N2V_EINVAL;
-  if (n_walks < 0 || walk_len < 1 || walk_len > N2V_SGNS_MAX_SENTENCE) return N2V_EINVAL;
-  if (P->n_vocab < 1 || P->dim < 1 || P->dim > 1024 || P->window < 1 || P->window > 32 ||
-      P->negative < 1 || P->negative > 32)
+  if (!n2v::check_common(P->n_vocab, P->dim, P->window, n_walks, walk_len) || P->negative < 1 || P->negative > 32)
     return N2V_EINVAL;
   if (P->batched != 0 && P->batched != 1) return N2V_EINVAL;
   if (dry_waves) *dry_waves = 0;
@@ -503,8 +499,7 @@ static int sgns_train_impl(const int32_t *walks, int64_t n_walks, int32_t walk_l
                                    sample_int, exp_table, P, pairs_out, stream);
   }
   using namespace n2v;
-  int V = 1;
-  while (64 * V < P->dim) V *= 2;
+  const int V = vec_of(P->dim);
   // the window cache (kRing): rows of 64 * V floats, 2 * window + 2 of them (12 or 16), when the
   // dimension fills the wave exactly and the ring fits beside the other per-wave buffers
   const int ring_rows = 2 * P->window + 2 <= 12 ? 12 : 16;
@@ -513,73 +508,25 @@ static int sgns_train_impl(const int32_t *walks, int64_t n_walks, int32_t walk_l
   if (P->window_cache == 1 && !ring_fits) return N2V_EINVAL;
   if (P->hub_rows < 0) return N2V_EINVAL;
   const bool use_ring = P->window_cache == 1;
-  const int sent_cap = (walk_len + 3) & ~3;
+  const int sent_cap = sent_cap_of(walk_len);
   const int ints_per_wave = (2 * sent_cap + (2 * P->window + 1) * P->negative + 3) & ~3;
   const size_t lds = kExpTable * sizeof(float) + (P->cum_index ? 0 : (kBuckets + 1 + 3) * sizeof(int32_t)) +
                      (size_t)kSgnsWaves * ((size_t)ints_per_wave + (use_ring ? (size_t)ring_rows * 64 * V : 0)) * 4;
-  // Hogwild concurrency is scaled to the model: unsynchronised waves are harmless
-  // while collisions on a row are rare (gensim runs <= 16 threads); on a tiny
-  // vocabulary thousands of racing waves would overwrite each other's updates.
-  // One wave per 32 vocabulary rows, up to the whole chip (8192 waves >= 256 K rows).
-  int64_t waves = P->n_vocab / 32;
-  if (waves < 1) waves = 1;
-  if (waves > n_walks) waves = n_walks;
-  if (P->max_waves > 0 && waves > P->max_waves) waves = P->max_waves;
-  int64_t blocks = (waves + kSgnsWaves - 1) / kSgnsWaves;
   if (P->cum_index && (P->cum_index_bits < 1 || P->cum_index_bits > 30)) return N2V_EINVAL;
-  dim3 block(kSgnsWaves * 64);
-  if (waves < kSgnsWaves) block = dim3((unsigned)waves * 64);
-  if (P->deterministic) {
-    blocks = 1;
-    block = dim3(64);
-  }
-  hipStream_t st = (hipStream_t)stream;
-  // pairs_out[1] is the kernel's row counter: start it at zero on the same stream
-  if (!dry_waves && pairs_out && hipMemsetAsync(pairs_out + 1, 0, sizeof(unsigned long long), st) != hipSuccess)
-    return N2V_ELAUNCH;
-  // lookahead depth: 1 pair for dim <= 512, none above (registers).  Depth 2 was measured
-  // in rounds 2 and 3 (ring variant) and lost every time.
-#define N2V_SGNS_DEPTH(VV) ((VV) <= 8 ? 1 : 0)
-#define N2V_LAUNCH_R(VV, RR)                                                                  \
-  do {                                                                                       \
-    constexpr int kD = N2V_SGNS_DEPTH(VV);                   \
-    const void *fn = (const void *)sgns_kernel<VV, kD, RR>;                                   \
-    if (lds > 64 * 1024 &&                                                                   \
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-      return N2V_ELAUNCH;                                                                    \
-    if (!P->deterministic) {                                                                 \
-      const int64_t cap = resident_blocks(fn, (int)block.x, lds);                            \
-      if (blocks > cap) blocks = cap;                                                        \
-    }                                                                                        \
-    if (dry_waves) {                                                                         \
-      *dry_waves = blocks * (int64_t)(block.x / 64);                                         \
-      break;                                                                                 \
-    }                                                                                        \
-    hipLaunchKernelGGL((sgns_kernel<VV, kD, RR>), dim3((unsigned)blocks), block, lds, st,     \
-                       walks, n_walks, walk_len, syn0, syn1neg, cum_table, sample_int,        \
-                       exp_table, *P, pairs_out, sent_cap);                                   \
-  } while (0)
-#define N2V_LAUNCH_RING(VV)         \
-  do {                              \
-    if (!use_ring)                  \
-      N2V_LAUNCH_R(VV, 0);          \
-    else if (ring_rows == 12)       \
-      N2V_LAUNCH_R(VV, 12);         \
-    else                            \
-      N2V_LAUNCH_R(VV, 16);         \
-  } while (0)
+  const LaunchGeometry geo = hogwild_geometry(P->n_vocab, n_walks, P->max_waves, P->deterministic, kSgnsWaves);
+  auto launch = [&](auto kernel) {
+    return launch_trainer(kernel, geo, lds, P->deterministic, pairs_out, stream, dry_waves, walks, n_walks, walk_len,
+                          syn0, syn1neg, cum_table, sample_int, exp_table, *P, pairs_out, sent_cap);
+  };
+  // sgns_kernel<VEC, kDepth, kRingRows>.  Lookahead depth: 1 pair for dim <= 512, none above (registers);
+  // depth 2 was measured in rounds 2 and 3 (ring variant) and lost every time.
   switch (V) {
-    case 1: N2V_LAUNCH_RING(1); break;
-    case 2: N2V_LAUNCH_RING(2); break;
-    case 4: N2V_LAUNCH_R(4, 0); break;
-    case 8: N2V_LAUNCH_R(8, 0); break;
-    default: N2V_LAUNCH_R(16, 0); break;
+    case 1: return launch_ring<1>(use_ring ? ring_rows : 0, launch);
+    case 2: return launch_ring<2>(use_ring ? ring_rows : 0, launch);
+    case 4: return launch(sgns_kernel<4, 1, 0>);
+    case 8: return launch(sgns_kernel<8, 1, 0>);
+    default: return launch(sgns_kernel<16, 0, 0>);
   }
-#undef N2V_LAUNCH_RING
-#undef N2V_LAUNCH_R
-  if (dry_waves) return N2V_OK;
-  N2V_HIP_CHECK(hipGetLastError());
-  return N2V_OK;
 }
 
 extern "C" int n2v_sgns_train(const int32_t *walks, int64_t n_walks, int32_t walk_len,

@@ -28,6 +28,7 @@
 // equal rows), and the accumulator layout (4 rows x 16 consecutive columns per lane group)
 // reads and writes 64 consecutive bytes per row.
 #include "n2v_common.h"
+#include "n2v_w2v_core.h"
 
 namespace n2v {
 
@@ -35,13 +36,6 @@ constexpr int kBWaves = 2;        // waves per block (LDS: ~16 KB per wave at di
 constexpr int kBExpTable = 1000;  // EXP_TABLE_SIZE
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__host__ __device__ inline uint64_t b_sentence_stream(uint64_t seed, uint64_t sentence_id) {
-  return mix64(seed ^ mix64(sentence_id + 0xA0761D6478BD642FULL));
-}
-__host__ __device__ inline uint64_t b_draw(uint64_t hs, uint64_t idx) {
-  return mix64(hs + (idx + 1ULL) * 0xE7037ED1A0B428DBULL);
-}
 
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -117,17 +111,6 @@ __device__ __forceinline__ float f4_at(const float4 &v, int k) {
   return k == 0 ? v.x : (k == 1 ? v.y : (k == 2 ? v.z : v.w));
 }
 
-__device__ __forceinline__ int b_bisect(const uint32_t *a, int lo, int hi, uint32_t x) {
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (a[mid] < x)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
 // VEC = dim / 64; TROWS = rows of the target tile (8: 1 + negative <= 8, two k-steps; else 16);
 // KC = k-steps over the context rows (3: 2 * window + 2 <= 12 ring rows, else 4 and 16 rows)
 template <int VEC, int TROWS, int KC>
@@ -195,15 +178,11 @@ __global__ __launch_bounds__(kBWaves * 64) void sgns_batched_kernel(
   for (int rI = 0; rI < 4; ++rI) t_of_r[rI] = tgt_of(4 * g4 + rI);
 
   for (;;) {
-    if (dynamic) {
-      unsigned int t = 0;
-      if (lane == 0) t = atomicAdd(row_counter, 1u);
-      rr = (int64_t)(unsigned int)rfl((int)t);
-    }
+    if (dynamic) rr = claim_row(row_counter, lane);
     if (rr >= n_walks) break;
     const int64_t r = readfirstlane_i64(rr);
     if (!dynamic) rr += n_waves;
-    const uint64_t hs = b_sentence_stream(P.seed, (uint64_t)(P.sentence_base + r));
+    const uint64_t hs = sentence_stream(P.seed, (uint64_t)(P.sentence_base + r));
     if (P.row_alpha) alpha = P.row_alpha[r];  // gensim: the rate of this sentence's job (a scalar load)
     // ---- sentence preparation: vocabulary filter, subsampling, reduced windows ----
     int nf = 0;
@@ -212,14 +191,14 @@ __global__ __launch_bounds__(kBWaves * 64) void sgns_batched_kernel(
       int32_t tok = t < walk_len ? walks[r * walk_len + t] : -1;
       bool keep = tok >= 0 && (int64_t)tok < P.n_vocab;
       if (keep && sample_int) {
-        const uint32_t rnd = (uint32_t)(b_draw(hs, 2ULL * (uint64_t)t) >> 32);
+        const uint32_t rnd = (uint32_t)(sentence_draw(hs, 2ULL * (uint64_t)t) >> 32);
         keep = !(sample_int[tok] < rnd);
       }
       const uint64_t mask = ballot64(keep);
       const int pos = nf + __popcll(mask & ((1ull << lane) - 1ull));
       if (keep) {
         sent[pos] = tok;
-        red[pos] = (int32_t)((uint32_t)(b_draw(hs, 2ULL * (uint64_t)t + 1ULL) >> 32) %
+        red[pos] = (int32_t)((uint32_t)(sentence_draw(hs, 2ULL * (uint64_t)t + 1ULL) >> 32) %
                              (uint32_t)window);
       }
       nf += __popcll(mask);
@@ -229,14 +208,14 @@ __global__ __launch_bounds__(kBWaves * 64) void sgns_batched_kernel(
       const int i = q / K, d = q - i * K;
       const uint64_t idx = 2ULL * (uint64_t)walk_len +
                            ((uint64_t)i * 2ULL * (uint64_t)window) * (uint64_t)K + (uint64_t)d;
-      const uint32_t x = (uint32_t)((b_draw(hs, idx) >> 16) % (uint64_t)domain);
+      const uint32_t x = (uint32_t)((sentence_draw(hs, idx) >> 16) % (uint64_t)domain);
       int blo = 0, bhi = (int)P.n_vocab;
       if (P.cum_index) {
         const uint32_t bk = x >> (31 - P.cum_index_bits);
         blo = P.cum_index[bk];
         bhi = P.cum_index[bk + 1];
       }
-      negw[q] = b_bisect(cum_table, blo, bhi, x);
+      negw[q] = bisect_range_u32(cum_table, blo, bhi, x);
     }
     wave_sync();
     if (nf < 2) continue;  // a single token has no context: nothing to train
@@ -609,6 +588,13 @@ __global__ __launch_bounds__(kBWaves * 64) void sgns_batched_kernel(
   if (pairs_out && lane == 0 && pairs) atomicAdd(pairs_out, pairs);
 }
 
+// the instance for a target tile of `trows` rows and `kc` k-steps over the context rows
+template <int VEC, typename Launch>
+static int launch_tiles(int trows, int kc, Launch launch) {
+  if (trows == 8) return kc == 3 ? launch(sgns_batched_kernel<VEC, 8, 3>) : launch(sgns_batched_kernel<VEC, 8, 4>);
+  return kc == 3 ? launch(sgns_batched_kernel<VEC, 16, 3>) : launch(sgns_batched_kernel<VEC, 16, 4>);
+}
+
 }  // namespace n2v
 
 extern "C" int n2v_sgns_batched_launch(const int32_t *walks, int64_t n_walks, int32_t walk_len,
@@ -631,51 +617,20 @@ extern "C" int n2v_sgns_batched_launch(const int32_t *walks, int64_t n_walks, in
   const int PL = P->negative + 1 + (trows == 8 ? 1 : 2) + 1;
   const size_t per_wave = ((size_t)(4 * PR + 4 * PT + 16 * 17) +
                            (size_t)((2 * walk_len + walk_len * PL + 32 + (own_negw ? walk_len * P->negative : 0) + 3) & ~3)) * 4;
-  int64_t waves = P->n_vocab / 32;
-  if (waves < 1) waves = 1;
-  if (waves > n_walks) waves = n_walks;
-  if (P->max_waves > 0 && waves > P->max_waves) waves = P->max_waves;
-  int wpb = kBWaves;
-  if (P->deterministic || waves < wpb) wpb = 1;
-  if (P->deterministic) waves = 1;
+  // a block is one or two waves: with two waves per block "fewer waves than a block holds" is one wave,
+  // which is this launcher's rule (one wave per block below kBWaves waves) -- only because kBWaves is 2
+  static_assert(kBWaves == 2, "hogwild_geometry's smaller block equals one wave per block only at kBWaves == 2");
+  const LaunchGeometry geo = hogwild_geometry(P->n_vocab, n_walks, P->max_waves, P->deterministic, kBWaves);
+  const int wpb = geo.block_threads / 64;
   const size_t lds = kBExpTable * sizeof(float) + (size_t)wpb * per_wave;
   if (lds > 160 * 1024) return N2V_EINVAL;
-  int64_t blocks = (waves + wpb - 1) / wpb;
-  hipStream_t st = (hipStream_t)stream;
-  if (pairs_out && hipMemsetAsync(pairs_out + 1, 0, sizeof(unsigned long long), st) != hipSuccess)
-    return N2V_ELAUNCH;
-#define N2V_BLAUNCH(VV, TT, KK)                                                                       \
-  do {                                                                                            \
-    const void *fn = (const void *)sgns_batched_kernel<VV, TT, KK>;                                   \
-    if (lds > 64 * 1024 &&                                                                        \
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-      return N2V_ELAUNCH;                                                                         \
-    if (!P->deterministic) {                                                                      \
-      const int64_t cap = resident_blocks(fn, wpb * 64, lds);                                     \
-      if (blocks > cap) blocks = cap;                                                             \
-    }                                                                                             \
-    hipLaunchKernelGGL((sgns_batched_kernel<VV, TT, KK>), dim3((unsigned)blocks), dim3(wpb * 64), lds, \
-                       st, walks, n_walks, walk_len, syn0, syn1neg, cum_table, sample_int,        \
-                       exp_table, *P, pairs_out, own_negw);                                          \
-  } while (0)
-#define N2V_BLAUNCH_T(VV)     \
-  do {                        \
-    if (trows == 8 && kc == 3)      \
-      N2V_BLAUNCH(VV, 8, 3);        \
-    else if (trows == 8)            \
-      N2V_BLAUNCH(VV, 8, 4);        \
-    else if (kc == 3)               \
-      N2V_BLAUNCH(VV, 16, 3);       \
-    else                            \
-      N2V_BLAUNCH(VV, 16, 4);       \
-  } while (0)
+  auto launch = [&](auto kernel) {
+    return launch_trainer(kernel, geo, lds, P->deterministic, pairs_out, stream, nullptr, walks, n_walks, walk_len,
+                          syn0, syn1neg, cum_table, sample_int, exp_table, *P, pairs_out, own_negw);
+  };
   switch (VEC) {
-    case 1: N2V_BLAUNCH_T(1); break;
-    case 2: N2V_BLAUNCH_T(2); break;
-    default: N2V_BLAUNCH_T(4); break;
+    case 1: return launch_tiles<1>(trows, kc, launch);
+    case 2: return launch_tiles<2>(trows, kc, launch);
+    default: return launch_tiles<4>(trows, kc, launch);
   }
-#undef N2V_BLAUNCH_T
-#undef N2V_BLAUNCH
-  N2V_HIP_CHECK(hipGetLastError());
-  return N2V_OK;
 }

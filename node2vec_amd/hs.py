@@ -7,14 +7,13 @@ maxSentenceLength in-vocabulary tokens, (rand - 0.5) / dim initialisation of syn
 and Spark's learning-rate rule per row.  Tensors live on the GPU; the arithmetic of training is
 the HIP kernel.
 """
-import math
 from typing import Optional
 
 import numpy as np
 import torch
 
 from node2vec_amd import _lib
-from node2vec_amd.sgns import MAX_SENTENCE, Vocab, exp_table, init_syn0, split_rows
+from node2vec_amd.sgns import MAX_SENTENCE, Vocab, default_block_rows, exp_table, init_syn0, split_rows
 
 RATE_REFRESH_WORDS = 10000  # Spark refreshes the learning rate every 10 000 words
 MIN_RATE_SHARE = 1e-4       # ... and never below stepSize * 1e-4
@@ -183,7 +182,7 @@ class HsModel:
         words = (rows_idx >= 0).sum(1).cpu().numpy()
         train_words = int(words.sum())
         if block_rows is None:
-            block_rows = max(1, min(max(rows, 1), max(65536, math.ceil(rows / 64))))
+            block_rows = default_block_rows(rows)
         for ep in range(int(epochs)):
             ra = torch.from_numpy(spark_row_alpha(words, ep, epochs, step_size, train_words)).to(rows_idx.device)
             for lo in range(0, rows, block_rows):

@@ -323,7 +323,7 @@ class SgnsModel:
         rows = walks_idx.shape[0]
         grid_rows = max(rows, int(rows_global_max or 0))
         if block_rows is None:
-            block_rows = max(1, min(max(grid_rows, 1), max(65536, math.ceil(grid_rows / 64))))
+            block_rows = default_block_rows(grid_rows)
         total = max(1, grid_rows * max(epochs, 1))
         done = 0
         if sync is not None and not hasattr(sync, "step"):
@@ -413,6 +413,12 @@ class _CallableSync:
 
     def finish(self):
         pass
+
+
+def default_block_rows(rows: int) -> int:
+    """Rows per launch of a training epoch when the caller names none: 64 launches per epoch, but at least
+    65536 rows each (and at most all of them)."""
+    return max(1, min(max(rows, 1), max(65536, math.ceil(rows / 64))))
 
 
 def split_rows(walks_idx: torch.Tensor, max_len: int = MAX_SENTENCE) -> torch.Tensor:

@@ -405,3 +405,52 @@ def test_job_alpha_entry_point_equals_python_floats():
     for bad in ((0, 0, 1, 0, 4, 0.1, 0.01, 4), (1, 0, 0, 0, 4, 0.1, 0.01, 4), (1, 0, 1, -1, 4, 0.1, 0.01, 4),
                 (1, 0, 1, 0, 0, 0.1, 0.01, 4)):
         assert L.n2v_sgns_job_alpha(*bad, out.data_ptr(), _lib.current_stream_ptr()) == _lib.EINVAL
+
+
+def _abi_params(cls, **kw):
+    from node2vec_amd import _lib
+
+    if cls == "hs":
+        d = dict(n_vocab=10, sentence_base=0, seed=1, dim=128, window=5, alpha=0.025, deterministic=0,
+                 row_alpha=None, max_waves=0, hot_nodes=0, path_cache=1, reserved=0)
+        d.update(kw)
+        return _lib.HsParams(**d)
+    d = dict(n_vocab=10, sentence_base=0, seed=1, dim=128, window=5, negative=5, alpha=0.025, deterministic=0,
+             cum_index_bits=0, cum_index=None, max_waves=0, batched=0, window_cache=0, hub_rows=0, row_alpha=None)
+    d.update(kw)
+    return _lib.SgnsParams(**d)
+
+
+def test_skip_gram_entry_refuses_a_vocabulary_of_2_to_the_31():
+    """tokens are int32: the dry-run query rejects before it touches memory (no model is allocated).
+    n2v_sgns_train runs the same checks (one function serves both entries, and the batched path behind
+    it); called without a model it would be refused for its null pointers first, so only the query can
+    show this refusal."""
+    from node2vec_amd import _lib
+
+    L = _lib.load()
+    for batched in (0, 1):
+        assert L.n2v_sgns_hogwild_waves(_abi_params("sgns", n_vocab=1 << 31, batched=batched), 10, 8) == _lib.EINVAL
+    assert L.n2v_sgns_hogwild_waves(_abi_params("sgns", n_vocab=(1 << 31) - 1), 10, 8) > 0
+
+
+def test_hogwild_waves_of_the_three_entries_are_what_they_were():
+    """n2v_{sgns,cbow,hs}_hogwild_waves at dim 128, sentences of 40 tokens, over vocabulary x sentences x
+    max_waves.  All but the last follow from the rule alone: one wave per 32 words, at most one per sentence
+    and max_waves, whole blocks of 4 waves from 4 waves on.  At 10^6 words the cap by resident blocks
+    decides: 256 CUs x 4 SIMDs x the kernel's waves per SIMD on an MI355X (8 for sgns_kernel<2, 1, 0>, 4 for
+    cbow_kernel<2> and hs_kernel<2>); on a part with another CU count or register file those three differ."""
+    from node2vec_amd import _lib
+
+    L = _lib.load()
+    # (n_vocab, n_walks, max_waves) -> waves
+    common = {(64, 3, 0): 2, (64, 3, 5): 2, (64, 100000, 0): 2, (64, 100000, 5): 2, (4096, 3, 0): 3, (4096, 3, 5): 3,
+              (4096, 100000, 0): 128, (4096, 100000, 5): 8, (10 ** 6, 3, 0): 3, (10 ** 6, 3, 5): 3,
+              (10 ** 6, 100000, 5): 8}
+    whole_chip = {"sgns": 8192, "cbow": 4096, "hs": 4096}
+    for name, fn in (("sgns", L.n2v_sgns_hogwild_waves), ("cbow", L.n2v_cbow_hogwild_waves),
+                     ("hs", L.n2v_hs_hogwild_waves)):
+        want = dict(common)
+        want[(10 ** 6, 100000, 0)] = whole_chip[name]
+        for (v, n, mw), waves in want.items():
+            assert fn(_abi_params(name, n_vocab=v, max_waves=mw), n, 40) == waves, (name, v, n, mw)
