@@ -342,7 +342,9 @@ int n2v_pivots_build(const int32_t *col, int64_t n_edges, int32_t *pivots_out, v
  * bit for bit; N2V_WALK_FAST draws from the same distribution by rejection.
  * With return_param == inout_param == 1 (the reference's defaults) and g->slots set,
  * exact mode reads the K1 tables instead of rebuilding them: same bits, one gather per
- * step. */
+ * step.  On a unit-weight graph a return_param == inout_param == 1 walk of up to 255 steps
+ * enqueues TWO kernels on `stream` (the walk, which stores each wave's rows step-major, and an
+ * in-place transpose of those regions): walks_out is complete when the stream has passed both. */
 int n2v_walk(const n2v_graph *g, const int32_t *start_ids, int64_t n_start,
              int32_t num_walks, int32_t walk_length, double return_param,
              double inout_param, uint64_t seed, int32_t mode,

@@ -10,11 +10,18 @@
 // 64-byte sector reads (scripts/micro/gather_ceiling.hip: ~25-27 G such steps/s), so what it
 // can save is requests:
 //   * one LANE per walker, 8 waves per SIMD, nothing else in flight;
-//   * the path is NOT stored word by word (a 4-byte store into a 324-byte-pitch row costs a
-//     32-byte write request each, as many requests as the reads): every lane keeps the 16
-//     words of the 64-byte sector of walks_out it is currently filling in registers
-//     (selected by a v_cndmask chain, no scratch) and stores the sector whole when it is
-//     complete -- four aligned 16-byte stores per 16 steps.
+//   * the path is NOT stored word by word into its row (a 4-byte store into a 324-byte-pitch row
+//     costs a 32-byte write request each, as many requests as the reads).  The rows of the 64
+//     walkers of a wave are one contiguous region of walks_out, and the kernel writes that region
+//     STEP-MAJOR: position pos of lane l at word pos * cnt + l of the region, one plain dword store
+//     per lane per step, 256 contiguous bytes per wave.  walk_chunk_transpose_kernel, launched right
+//     behind on the same stream, turns every region row-major in place through LDS (one block per
+//     region).  A p = q = 1 walk is therefore TWO kernels, and a kernel trace shows its time as
+//     their sum.
+//   * walks too long for the transpose tile (walk_length + 1 > kChunkMaxL1) keep the earlier
+//     form, in one kernel: every lane holds the 16 words of the 64-byte sector of walks_out it is
+//     filling in registers (selected by a v_cndmask chain, no scratch) and stores the sector
+//     whole when it is complete -- four aligned 16-byte stores per 16 steps.
 //   * with the hop table (n2v_hops_build, 16 bytes per edge: neighbour id + its row pointer
 //     and degree) the two dependent gathers of a step become ONE: the entry that names the next
 //     vertex also says where its row starts and how long it is.  The chip sustains ~50 G random
@@ -60,12 +67,72 @@ __device__ __forceinline__ void rank_row(const n2v_graph &g, const uint32_t *fir
   vb = (int64_t)(o0 + (x - f0) * d);  // < n_edges < 2^32
 }
 
+// The transpose tile of a full region is 64 * L1 words of LDS: 64 KB at L1 == 256, the most a block
+// may ask for.  Longer walks take the register-sector path.
+constexpr int kChunkMaxL1 = 256;
+
+// Where the words of a path go.  The step-major form: the region of the wave that starts at walker
+// `base` holds cnt = min(64, total - base) rows of L1 words, position pos of lane l at word
+// pos * cnt + l of it.
+template <bool kChunked>
+struct path_writer;
+
+template <>
+struct path_writer<true> {
+  int32_t *at;  // this lane's word of position 0
+  int cnt;
+  __device__ __forceinline__ path_writer(int32_t *walks_out, int64_t base, int64_t total, int L1, int lane,
+                                         int64_t)
+      : at(walks_out + base * (int64_t)L1 + lane), cnt((int)(total - base < 64 ? total - base : 64)) {}
+  __device__ __forceinline__ void put(int pos, int32_t x, int) { at[pos * cnt] = x; }  // pos * cnt < 2^14
+};
+
+// The row-major form without a second kernel: word a of walks_out lives in buf[a & 15] until its
+// 64-byte sector (or the row) is complete, and is then stored with it.
+template <>
+struct path_writer<false> {
+  int32_t *walks_out;
+  int64_t w0;  // absolute word index of path position 0
+  int lo;      // first word of the current sector that belongs to this row
+  bool base_aligned;  // whole sectors need a 64-byte aligned output base (torch / hipMalloc give >= 256)
+  int32_t buf[16];
+  __device__ __forceinline__ path_writer(int32_t *out, int64_t, int64_t, int L1, int, int64_t r)
+      : walks_out(out), w0(r * (int64_t)L1), lo((int)((r * (int64_t)L1) & 15)),
+        base_aligned((reinterpret_cast<uintptr_t>(out) & 63u) == 0) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) buf[k] = -1;
+  }
+  __device__ __forceinline__ void put(int pos, int32_t x, int walk_length) {
+    const int64_t a = w0 + pos;
+    const int k = (int)(a & 15);
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) buf[kk] = (k == kk) ? x : buf[kk];
+    if (k != 15 && pos != walk_length) return;
+    // words [sector(a) + lo, a] are complete: store them
+    int32_t *sec = walks_out + (a & ~(int64_t)15);
+    if (lo == 0 && k == 15 && base_aligned) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        reinterpret_cast<int4 *>(sec)[u] =
+            make_int4(buf[4 * u], buf[4 * u + 1], buf[4 * u + 2], buf[4 * u + 3]);
+    } else {
+#pragma unroll
+      for (int kk = 0; kk < 16; ++kk)
+        if (kk >= lo && kk <= k) sec[kk] = buf[kk];
+    }
+    lo = 0;
+  }
+};
+
 // kHops: 0 = CSR arrays (two gathers per step), 1 = the 16-byte hop table, 2 = the 8-byte hop
 // table (round 3: the chip serves 8-byte gathers over a table half the size a quarter faster),
 // 3 = the degree-ranked 4-byte table (blocks of 1024 threads, the class table in LDS: up to 8191
 // classes in 64 KB, two blocks per CU), 4 = the same frame on the 8-byte {vertex id, rank} pair table
 // (g.rank_hops points at uint64 entries; vertex ids out)
-template <int kHops, int kThreads>
+//
+// kChunked: the step-major region per wave (walk_chunk_transpose_kernel must follow); otherwise
+// whole sectors of the row-major output from registers
+template <int kHops, int kThreads, bool kChunked>
 __global__ __launch_bounds__(kThreads, 8) void walk_uniform_kernel(
     n2v_graph g, const int32_t *__restrict__ start_ids, int64_t n_start, int32_t num_walks,
     int32_t walk_length, uint64_t seed, int32_t *__restrict__ walks_out,
@@ -73,8 +140,6 @@ __global__ __launch_bounds__(kThreads, 8) void walk_uniform_kernel(
   const int lane = threadIdx.x & 63;
   const int64_t total = n_start * (int64_t)num_walks;
   const int L1 = walk_length + 1;
-  // whole sectors need a 64-byte aligned output base (torch / hipMalloc give >= 256)
-  const bool base_aligned = (reinterpret_cast<uintptr_t>(walks_out) & 63u) == 0;
   extern __shared__ uint32_t rank_lds[];
   const uint32_t *cls_first = rank_lds;
   const uint32_t *cls_where = rank_lds + (kHops >= 3 ? g.rank_classes : 0);
@@ -122,36 +187,9 @@ __global__ __launch_bounds__(kThreads, 8) void walk_uniform_kernel(
       if (kHops == 2 && g.hop8_rowptr) vb = g.hop8_rowptr[v];  // the padded table's own row start
     }
     bool walking = alive;
-    // absolute word index of path position 0; word a lives in buf[a & 15]
-    const int64_t w0 = r * (int64_t)L1;
-    int32_t buf[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) buf[k] = -1;
-    int lo = (int)(w0 & 15);  // first word of the current sector that belongs to this row
-    auto put = [&](int64_t a, int32_t x) {
-      const int k = (int)(a & 15);
-#pragma unroll
-      for (int kk = 0; kk < 16; ++kk) buf[kk] = (k == kk) ? x : buf[kk];
-    };
-    auto flush = [&](int64_t a) {  // words [sector(a) + lo, a] are complete: store them
-      const int k = (int)(a & 15);
-      int32_t *sec = walks_out + (a & ~(int64_t)15);
-      if (lo == 0 && k == 15 && base_aligned) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          reinterpret_cast<int4 *>(sec)[u] =
-              make_int4(buf[4 * u], buf[4 * u + 1], buf[4 * u + 2], buf[4 * u + 3]);
-      } else {
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk)
-          if (kk >= lo && kk <= k) sec[kk] = buf[kk];
-      }
-      lo = 0;
-    };
-    if (have) {
-      put(w0, alive ? v_emit : -1);
-      if ((w0 & 15) == 15 || walk_length == 0) flush(w0);
-    }
+    // the path: position pos of this lane's row
+    auto emit = path_writer<kChunked>(walks_out, base, total, L1, lane, r);
+    if (have) emit.put(0, alive ? v_emit : -1, walk_length);
     for (int step = 0; step < walk_length; ++step) {
       if (ballot64(have) == 0ull) break;
       int32_t x = -1;
@@ -193,14 +231,87 @@ __global__ __launch_bounds__(kThreads, 8) void walk_uniform_kernel(
           alive = false;
         }
       }
-      if (have) {
-        const int64_t a = w0 + step + 1;
-        put(a, x);
-        if ((a & 15) == 15 || step + 1 == walk_length) flush(a);
-      }
+      if (have) emit.put(step + 1, x, walk_length);
     }
     if (have) valid_out[r] = alive ? 1 : 0;
   }
+}
+
+// Turns the step-major region of every wave of walk_uniform_kernel<.., true> row-major, in place: a
+// block per region at a time (a resident grid whose blocks take regions in turn), the region's
+// cnt * L1 words through LDS (dynamic, 4 * 64 * L1 bytes).  Dword accesses to walks, so an output
+// base aligned to 4 bytes serves.  A full region's row is rotated on its way into LDS: (pos, l) lies
+// at pos * 64 + ((l * m + pos) & 63) with m = L1 | 1.  m is odd, so the 32 lanes of a ds_write
+// group, which share pos and hold consecutive l, fall on 32 different banks; on the way out lane i
+// reads (pos, row) = (i % L1, i / L1) from bank (row * m + pos) % 32, which is i % 32 for an odd L1
+// (no conflict at all, the headline's 81) and (i + row) % 32 for an even one (two lanes of a group
+// share a bank where the group crosses into its next row).  The one partial region of a launch is
+// not rotated (64 would have to be cnt, and l -> l * m % cnt a bijection).  A thread moves its words
+// kBatch at a time, all loads of a batch issued before the first is used.  The kernel reads and
+// writes every word of walks_out once (2 x 3.4 GB at the headline) and runs at the HBM rate.
+constexpr int kTransposeThreads = 256, kTransposeBatch = 8;
+
+template <int kThreads, int kBatch>
+__global__ __launch_bounds__(kThreads) void walk_chunk_transpose_kernel(int32_t *__restrict__ walks,
+                                                                        int64_t total, int32_t L1) {
+  extern __shared__ int32_t tile[];
+  const int m = L1 | 1;
+  const int row0 = (int)threadIdx.x / L1, pos0 = (int)threadIdx.x % L1;
+  const int drow = kThreads / L1, dpos = kThreads % L1;
+  int32_t x[kBatch];
+  for (int64_t base = (int64_t)blockIdx.x * 64; base < total; base += (int64_t)gridDim.x * 64) {
+    const int cnt = (int)(total - base < 64 ? total - base : 64);
+    int32_t *region = walks + base * (int64_t)L1;
+    const int n = cnt * L1;
+    const bool full = cnt == 64;
+    for (int i0 = threadIdx.x; i0 < n; i0 += kThreads * kBatch) {
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int i = i0 + u * kThreads;
+        x[u] = i < n ? region[i] : 0;
+      }
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int i = i0 + u * kThreads;
+        const int pos = i >> 6, l = i & 63;
+        if (i < n) tile[full ? (pos << 6) + ((l * m + pos) & 63) : i] = x[u];
+      }
+    }
+    __syncthreads();
+    int row = row0, pos = pos0;
+    for (int i0 = threadIdx.x; i0 < n; i0 += kThreads * kBatch) {
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        x[u] = i0 + u * kThreads < n ? tile[pos * cnt + (full ? ((row * m + pos) & 63) : row)] : 0;
+        row += drow;
+        pos += dpos;
+        if (pos >= L1) {
+          pos -= L1;
+          ++row;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int i = i0 + u * kThreads;
+        if (i < n) region[i] = x[u];
+      }
+    }
+    __syncthreads();  // the tile is free for the block's next region
+  }
+}
+
+// one launch of walk_uniform_kernel<kHops, kThreads, kChunked> over as many blocks as are resident
+template <int kHops, int kThreads, bool kChunked>
+static hipError_t launch_walk_uniform(const n2v_graph *g, const int32_t *start_ids, int64_t n_start,
+                                      int32_t num_walks, int32_t walk_length, uint64_t seed, int32_t *walks_out,
+                                      uint8_t *valid_out, uint32_t *status, size_t lds, hipStream_t stream) {
+  const auto fn = walk_uniform_kernel<kHops, kThreads, kChunked>;
+  int64_t blocks = (n_start * (int64_t)num_walks + kThreads - 1) / kThreads;
+  const int64_t cap = resident_blocks((const void *)fn, kThreads, lds);
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kThreads), lds, stream, *g, start_ids, n_start, num_walks,
+                     walk_length, seed, walks_out, valid_out, status);
+  return hipGetLastError();
 }
 
 }  // namespace n2v
@@ -232,42 +343,40 @@ extern "C" int n2v_walk_uniform_try(const n2v_graph *g, const int32_t *start_ids
   // status[1] is the kernel's walker counter: start it at zero on the same stream
   if (hipMemsetAsync(status + 1, 0, sizeof(uint32_t), (hipStream_t)stream) != hipSuccess)
     return N2V_ELAUNCH;
-  int64_t blocks = (total + 255) / 256;
-  if (form >= 3) {
-    const size_t lds = (size_t)g->rank_classes * 8;
-    const void *fn3 = form == 4 ? (const void *)n2v::walk_uniform_kernel<4, 1024>
-                                : (const void *)n2v::walk_uniform_kernel<3, 1024>;
-    blocks = (total + 1023) / 1024;
-    const int64_t cap3 = n2v::resident_blocks(fn3, 1024, lds);
-    if (blocks > cap3) blocks = cap3;
-#define N2V_RANKED_LAUNCH(F)                                                                          \
-  hipLaunchKernelGGL((n2v::walk_uniform_kernel<F, 1024>), dim3((unsigned)blocks), dim3(1024), lds,    \
-                     (hipStream_t)stream, *g, start_ids, n_start, num_walks, walk_length, seed,       \
-                     walks_out, valid_out, status)
-    if (form == 4)
-      N2V_RANKED_LAUNCH(4);
-    else
-      N2V_RANKED_LAUNCH(3);
-#undef N2V_RANKED_LAUNCH
-    if (hipGetLastError() != hipSuccess) return N2V_ELAUNCH;
-    return 1;
-  }
-  const void *fn = form == 2   ? (const void *)n2v::walk_uniform_kernel<2, 256>
-                   : form == 1 ? (const void *)n2v::walk_uniform_kernel<1, 256>
-                               : (const void *)n2v::walk_uniform_kernel<0, 256>;
-  const int64_t cap = n2v::resident_blocks(fn, 256, 0);
-  if (blocks > cap) blocks = cap;
-#define N2V_UNIFORM_LAUNCH(F)                                                                     \
-  hipLaunchKernelGGL((n2v::walk_uniform_kernel<F, 256>), dim3((unsigned)blocks), dim3(256), 0,   \
-                     (hipStream_t)stream, *g, start_ids, n_start, num_walks, walk_length, seed,  \
-                     walks_out, valid_out, status)
-  if (form == 2)
-    N2V_UNIFORM_LAUNCH(2);
+  const hipStream_t s = (hipStream_t)stream;
+  const size_t lds = form >= 3 ? (size_t)g->rank_classes * 8 : 0;
+  const bool chunked = walk_length + 1 <= n2v::kChunkMaxL1;
+  hipError_t e = hipSuccess;
+#define N2V_UNIFORM_LAUNCH(F, T)                                                                             \
+  e = chunked ? n2v::launch_walk_uniform<F, T, true>(g, start_ids, n_start, num_walks, walk_length, seed,    \
+                                                     walks_out, valid_out, status, lds, s)                   \
+              : n2v::launch_walk_uniform<F, T, false>(g, start_ids, n_start, num_walks, walk_length, seed,   \
+                                                      walks_out, valid_out, status, lds, s)
+  if (form == 4)
+    N2V_UNIFORM_LAUNCH(4, 1024);
+  else if (form == 3)
+    N2V_UNIFORM_LAUNCH(3, 1024);
+  else if (form == 2)
+    N2V_UNIFORM_LAUNCH(2, 256);
   else if (form == 1)
-    N2V_UNIFORM_LAUNCH(1);
+    N2V_UNIFORM_LAUNCH(1, 256);
   else
-    N2V_UNIFORM_LAUNCH(0);
+    N2V_UNIFORM_LAUNCH(0, 256);
 #undef N2V_UNIFORM_LAUNCH
-  if (hipGetLastError() != hipSuccess) return N2V_ELAUNCH;
+  if (e != hipSuccess) return N2V_ELAUNCH;
+  if (chunked) {
+    // the regions the walk kernel wrote step-major, row-major in place: walks_out is complete when the
+    // stream has passed this second kernel
+    int64_t chunks = (total + 63) / 64;  // < 2^26
+    const size_t tile = (size_t)64 * (size_t)(walk_length + 1) * sizeof(int32_t);
+    const int64_t cap = n2v::resident_blocks(
+        (const void *)n2v::walk_chunk_transpose_kernel<n2v::kTransposeThreads, n2v::kTransposeBatch>,
+        n2v::kTransposeThreads, tile);
+    if (chunks > cap) chunks = cap;
+    hipLaunchKernelGGL((n2v::walk_chunk_transpose_kernel<n2v::kTransposeThreads, n2v::kTransposeBatch>),
+                       dim3((unsigned)chunks), dim3(n2v::kTransposeThreads),
+                       tile, s, walks_out, total, walk_length + 1);
+    if (hipGetLastError() != hipSuccess) return N2V_ELAUNCH;
+  }
   return 1;
 }
