@@ -969,6 +969,34 @@ int n2v_kmeans_step(const float *X, const float *inv_norm, int64_t n, int32_t di
                     int64_t *counts_out, int64_t *stats_out, void *workspace, int64_t workspace_bytes,
                     void *stream);
 
+/* One-vs-rest L2 logistic regression over trained vectors (the node2vec paper's multi-label classification,
+ * section 4.3; csrc/n2v_logreg.hip, DESIGN.md "Node classification").  ADDITIONS ONLY: N2V_ABI_VERSION stays 15.
+ * X: row-major fp32 [n, dim], 1 <= dim <= 1024, 0 <= n < 2^31; W: fp32 [c, dim], b: fp32 [c], 1 <= c <= 1024;
+ * y_bits: uint32 [n][ceil(c / 32)], bit j of word w of a row is its label of class 32 w + j.
+ * z[r][k] = dot(W_k, x_r) + b[k], dot being the fixed fmaf chain of the nearest-neighbour and k-means kernels.
+ * Every result is a function of the arguments alone, bit for bit (no float atomics; the orders and the spelled
+ * exp / log1p are written out in csrc/n2v_logreg.hip and restated in tests/cpu_logreg/n2v_logreg_cpu.c).
+ * Argument errors are N2V_EINVAL before any launch: sizes out of range, then (n > 0) a NULL pointer, a
+ * workspace that is NULL, not 16-byte aligned or smaller than n2v_logreg_workspace_bytes.  n == 0 is N2V_OK,
+ * launches nothing and writes nothing. */
+
+/* Rows per slab of the gradient's fixed order of summation (a multiple of 64; -1 for sizes the calls refuse):
+ * round_up(max(1, ceil(n / S)), 64) with S = min(2048, 512 MiB / (4 c (dim + 3))) slabs at most. */
+int64_t n2v_logreg_slab_rows(int64_t n, int32_t dim, int32_t c);
+/* Bytes of workspace of the two calls below (-1 for sizes they refuse, 0 for n == 0): W padded to
+ * [round_up(c, 64)][round_up(dim, 16)], plus per slab fp32 [c, dim] and [c] and fp64 [c] partials, <= 512 MiB
+ * whatever n is, plus one more fp64 block (each part rounded up to 256 bytes). */
+int64_t n2v_logreg_workspace_bytes(int64_t n, int32_t dim, int32_t c);
+/* scores_out[r, k] = z[r][k], fp32 [n, c] row-major. */
+int n2v_logreg_scores(const float *X, int64_t n, int32_t dim, const float *W, const float *b, int32_t c,
+                      float *scores_out, void *workspace, int64_t workspace_bytes, void *stream);
+/* One pass over X: loss_out[0] = sum over (r, k) of the logistic loss l(z[r][k], y[r][k]), grad_w_out[k, d] =
+ * sum_r (sigmoid(z[r][k]) - y[r][k]) x_r[d] (fp64 [c, dim]), grad_b_out[k] = sum_r (sigmoid - y) (fp64 [c]):
+ * unregularised sums, not means; fp32 chains per slab of rows, folded over the slabs in fp64. */
+int n2v_logreg_loss_grad(const float *X, const uint32_t *y_bits, int64_t n, int32_t dim, const float *W,
+                         const float *b, int32_t c, double *loss_out, double *grad_w_out, double *grad_b_out,
+                         void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,381 @@
+// n2v_logreg.hip -- one-vs-rest logistic regression over a row-major fp32 matrix X[n, dim]: the scores
+// z[r][k] = dot(W_k, x_r) + b[k] of c classes, and in one launch that reads X once the summed logistic loss and its
+// gradient by W and b.  A block scores 64 rows against 16 or 64 classes at a time with the MFMA chain of
+// n2v_score_tile.h, turns the scores into residuals that stay in LDS, and multiplies them with the same rows
+// (still in L1 / L2) into the slab's partial gradient with a second MFMA chain whose k axis is the rows; a
+// finishing kernel folds the slabs in fp64.  No float atomics; every result is a function of (X, y, W, b) alone
+// (DESIGN.md "Node classification"; tests/cpu_logreg/n2v_logreg_cpu.c restates it).
+//
+// Per (row, class), y the label bit:  e = exp(-|z|);  p = (z >= 0 ? 1 : e) / (1 + e);  res = p - y;
+//   l = (m > 0 ? m : 0) + log1p(e) with m = y ? -z : z.  exp and log1p are the fmaf sequences spelled below.
+// Rows are cut into slabs of slab_rows(n, dim, c) (a multiple of 64).  Per slab s:
+//   GW[s][k][d]: acc = +0; acc = fmaf(res[r][k], x_r[d], acc) over the slab's rows ascending, then over the rows
+//                that pad the slab to a multiple of 64 acc = fmaf(+0, +0, acc): a -0 accumulator becomes +0.
+//   Gb[s][k]:    acc = +0; acc = acc + res[r][k] over the slab's rows ascending.
+//   L[s][k]:     acc = 0.0; acc = acc + (double)l[r][k] over the slab's rows ascending.
+// gW, gb and Lk are fp64 chains from 0.0 over s ascending of the (double) partials; loss = 0.0 + Lk[0] + Lk[1] ..
+#include <math.h>
+
+#include "n2v_score_tile.h"
+
+namespace {
+
+constexpr int kStepRows = 64;                  // rows per block step: 16 per wave, 4 waves
+constexpr int kMaxSlabs = 2048;                // blocks of the launch (8 per CU)
+constexpr int64_t kPartialsCap = 512ll << 20;  // bytes of slab partials at most
+constexpr int kMaxClasses = 1024;
+
+struct Plan {
+  int64_t slab_rows, c_pad, wpad_bytes, gw_bytes, gb_bytes, l_bytes, lk_bytes;
+  int32_t n_slabs;
+};
+
+Plan plan_of(int64_t n, int32_t dim, int32_t c) {
+  Plan p{};
+  const int64_t per_slab = 4 * (int64_t)c * (dim + 3);  // GW and Gb in fp32, L in fp64
+  int64_t most = kPartialsCap / per_slab;                // >= 127: per_slab <= 4 MiB + 12 KiB
+  if (most > kMaxSlabs) most = kMaxSlabs;
+  const int64_t share = (n + most - 1) / most;
+  p.slab_rows = round_up(share < 1 ? 1 : share, kStepRows);
+  p.n_slabs = (int32_t)((n + p.slab_rows - 1) / p.slab_rows);
+  p.c_pad = round_up(c, 64);
+  p.wpad_bytes = round_up(p.c_pad * dim_pad_of(dim) * 4, 256);
+  p.gw_bytes = round_up((int64_t)p.n_slabs * c * dim * 4, 256);
+  p.gb_bytes = round_up((int64_t)p.n_slabs * c * 4, 256);
+  p.l_bytes = round_up((int64_t)p.n_slabs * c * 8, 256);
+  p.lk_bytes = round_up((int64_t)c * 8, 256);
+  return p;
+}
+
+// exp(t) for t <= 0 (NaN: NaN; t < -104: 0).  n = rintf(t log2 e); r = t - n ln 2 in two fmaf (n times the high
+// part is exact); a degree-6 Horner chain; 2^n as two powers of two: exact while the result is normal
+__device__ inline float exp_neg(float t) {
+  if (!(t >= -104.0f)) return t != t ? t : 0.0f;
+  const float n = rintf(t * 0x1.715476p+0f);
+  float r = __fmaf_rn(n, -0x1.62e4p-1f, t);
+  r = __fmaf_rn(n, -0x1.7f7d1cp-20f, r);
+  float p = 0x1.6d7544p-10f;
+  p = __fmaf_rn(p, r, 0x1.126fb8p-7f);
+  p = __fmaf_rn(p, r, 0x1.5554acp-5f);
+  p = __fmaf_rn(p, r, 0x1.555404p-3f);
+  p = __fmaf_rn(p, r, 0x1.0p-1f);
+  p = __fmaf_rn(p, r, 1.0f);
+  p = __fmaf_rn(p, r, 1.0f);
+  const int32_t ni = (int32_t)n;
+  const int32_t n1 = ni / 2, n2 = ni - n1;
+  const float s1 = __uint_as_float((uint32_t)(n1 + 127) << 23), s2 = __uint_as_float((uint32_t)(n2 + 127) << 23);
+  return (p * s1) * s2;
+}
+
+// log1p(e) for e in [0, 1] (NaN: NaN): e + e^2 g(e), g a degree-13 Horner chain
+__device__ inline float log1p01(float e) {
+  float g = 0x1.e52a08p-12f;
+  g = __fmaf_rn(g, e, -0x1.eb08aap-9f);
+  g = __fmaf_rn(g, e, 0x1.d275c6p-7f);
+  g = __fmaf_rn(g, e, -0x1.18da6ep-5f);
+  g = __fmaf_rn(g, e, 0x1.ed6386p-5f);
+  g = __fmaf_rn(g, e, -0x1.5d27a2p-4f);
+  g = __fmaf_rn(g, e, 0x1.b16db6p-4f);
+  g = __fmaf_rn(g, e, -0x1.fa5fep-4f);
+  g = __fmaf_rn(g, e, 0x1.241036p-3f);
+  g = __fmaf_rn(g, e, -0x1.5545d4p-3f);
+  g = __fmaf_rn(g, e, 0x1.99987ap-3f);
+  g = __fmaf_rn(g, e, -0x1.fffff6p-3f);
+  g = __fmaf_rn(g, e, 0x1.555556p-2f);
+  g = __fmaf_rn(g, e, -0x1.0p-1f);
+  const float u = e * g;
+  return __fmaf_rn(e, u, e);
+}
+
+// W padded to [c_pad][dim_pad] with zeros; one wave per padded row
+__global__ __launch_bounds__(256) void prep_kernel(const float *__restrict__ W, int32_t c, int64_t c_pad, int32_t dim,
+                                                   float *__restrict__ wpad) {
+  const int lane = threadIdx.x & 63;
+  const int32_t dp = dim_pad_of(dim);
+  const int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (k >= c_pad) return;
+  const bool live = k < c;
+  const float *v = W + (live ? k : 0) * dim;
+  for (int d = lane; d < dp; d += 64) wpad[k * dp + d] = (live && d < dim) ? v[d] : 0.f;
+}
+
+// a wave scores 16 rows per step against every class; the steps of 64 rows go round the grid
+template <int G, bool VEC>
+__global__ __launch_bounds__(256) void scores_kernel(const float *__restrict__ X, int64_t n, int32_t dim,
+                                                     const float *__restrict__ wpad, const float *__restrict__ b,
+                                                     int32_t c, float *__restrict__ Z) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int32_t dp = dim_pad_of(dim);
+  for (int64_t base = (int64_t)blockIdx.x * kStepRows; base < n; base += (int64_t)gridDim.x * kStepRows) {
+    const int64_t row0 = base + 16 * wave;
+    if (row0 >= n) continue;
+    for (int32_t c0 = 0; c0 < c; c0 += 16 * G) {
+      f32x4 acc[G];
+      score_tile<G, VEC>(X, dim, row0, n, wpad + (int64_t)c0 * dp, lane, acc);
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const int32_t k = c0 + 16 * g + (lane & 15);
+        if (k >= c) continue;
+        const float bk = b[k];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int64_t r = row0 + 4 * (lane >> 4) + i;
+          if (r < n) Z[r * c + k] = acc[g][i] + bk;
+        }
+      }
+    }
+  }
+}
+
+// Block s owns slab s: rows [s slab_rows, ..).  Per step of 64 rows and per chunk of 16 G classes: the scoring
+// half leaves res and l of the step in LDS; the gradient half adds res^T x to the slab's partial (a lane owns its
+// accumulator elements for the whole slab: it stores them after a step and loads them before the next).
+template <int G, bool VEC>
+__global__ __launch_bounds__(256) void loss_grad_kernel(const float *__restrict__ X,
+                                                        const uint32_t *__restrict__ y_bits, int64_t n, int32_t dim,
+                                                        const float *__restrict__ wpad, const float *__restrict__ b,
+                                                        int32_t c, float *__restrict__ GW, float *__restrict__ Gb,
+                                                        double *__restrict__ L, int64_t slab_rows) {
+  constexpr int kChunk = 16 * G;      // classes per chunk
+  // floats per LDS row, 16 mod 32: the two rows that the 32 lanes of one LDS pass read for operand A sit 16 banks
+  // apart (no conflict); the scoring half's writes, rows 4 apart, are 2-way conflicts
+  constexpr int kStride = G == 1 ? 48 : 80;
+  __shared__ float sres[kStepRows * kStride];
+  __shared__ float sl[kStepRows * kStride];
+  __shared__ float sgb[kMaxClasses];
+  __shared__ double sloss[kMaxClasses];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int32_t dp = dim_pad_of(dim);
+  const int32_t words = (c + 31) >> 5;
+  const int64_t lo = (int64_t)blockIdx.x * slab_rows;
+  const int64_t hi = lo + slab_rows < n ? lo + slab_rows : n;
+  float *mine = GW + (int64_t)blockIdx.x * c * dim;
+  // thread tid < kChunk owns class c0 + tid of every chunk, here and below
+  if (tid < kChunk)
+    for (int32_t k = tid; k < c; k += kChunk) sgb[k] = 0.f, sloss[k] = 0.0;
+
+  for (int64_t base = lo; base < hi; base += kStepRows) {
+    const int cnt = hi - base < kStepRows ? (int)(hi - base) : kStepRows;
+    const int64_t row0 = base + 16 * wave;
+    const bool first = base == lo;
+    for (int32_t c0 = 0; c0 < c; c0 += kChunk) {
+      {
+        f32x4 acc[G];
+        score_tile<G, VEC>(X, dim, row0, hi, wpad + (int64_t)c0 * dp, lane, acc);
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          const int32_t k = c0 + 16 * g + (lane & 15);
+          const float bk = k < c ? b[k] : 0.f;
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            sres[(16 * wave + 4 * (lane >> 4) + i) * kStride + 16 * g + (lane & 15)] = acc[g][i] + bk;
+        }
+      }
+      // a lane turns the scores it has just written into residuals, one at a time (a rolled loop: few registers)
+#pragma unroll 1
+      for (int j = 0; j < 4 * G; ++j) {
+        const int g = j >> 2, i = j & 3;
+        const int32_t k = c0 + 16 * g + (lane & 15);
+        const int rl = 16 * wave + 4 * (lane >> 4) + i;
+        const int64_t r = base + rl;
+        float res = 0.f, l = 0.f;
+        if (r < hi && k < c) {
+          const uint32_t y = (y_bits[r * words + (k >> 5)] >> (k & 31)) & 1u;
+          const float z = sres[rl * kStride + 16 * g + (lane & 15)];
+          const float e = exp_neg(-fabsf(z));
+          const float num = z >= 0.0f ? 1.0f : e;
+          const float den = 1.0f + e;
+          const float p = num / den;
+          const float m = y ? -z : z;
+          res = p - (y ? 1.0f : 0.0f);
+          l = (m > 0.0f ? m : 0.0f) + log1p01(e);
+        }
+        sres[rl * kStride + 16 * g + (lane & 15)] = res;
+        sl[rl * kStride + 16 * g + (lane & 15)] = l;
+      }
+      __syncthreads();
+      if (tid < kChunk && c0 + tid < c) {
+        float gb = sgb[c0 + tid];
+        double ls = sloss[c0 + tid];
+        for (int i = 0; i < cnt; ++i) {
+          gb = gb + sres[i * kStride + tid];
+          ls = ls + (double)sl[i * kStride + tid];
+        }
+        sgb[c0 + tid] = gb;
+        sloss[c0 + tid] = ls;
+      }
+      // gradient: D[class][d] += sum over the step's rows of res[row][class] x[row][d]; operand A is res (lane l:
+      // class l & 15, row l >> 4), operand B is x (d l & 15, row l >> 4); four rows per MFMA, ascending
+      for (int32_t d0 = 16 * wave; d0 < dp; d0 += 64) {
+        const int32_t d = d0 + (lane & 15);
+        float xb[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int64_t r = base + 4 * q + (lane >> 4);
+          xb[q] = (r < hi && d < dim) ? X[r * (int64_t)dim + d] : 0.f;
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          const int32_t k0 = c0 + 16 * g + 4 * (lane >> 4);
+          if (c0 + 16 * g >= c) break;
+          f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+          if (!first && d < dim) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              if (k0 + i < c) acc[i] = mine[(int64_t)(k0 + i) * dim + d];
+          }
+#pragma unroll
+          for (int q = 0; q < 16; ++q) {
+            const float a = sres[(4 * q + (lane >> 4)) * kStride + 16 * g + (lane & 15)];
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xb[q], acc, 0, 0, 0);
+          }
+          if (d < dim) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              if (k0 + i < c) mine[(int64_t)(k0 + i) * dim + d] = acc[i];
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (tid < kChunk)
+    for (int32_t k = tid; k < c; k += kChunk) {
+      Gb[(int64_t)blockIdx.x * c + k] = sgb[k];
+      L[(int64_t)blockIdx.x * c + k] = sloss[k];
+    }
+}
+
+// the slab partials folded in ascending slab order in fp64: a thread per element of gW, then of gb and Lk
+__global__ __launch_bounds__(256) void fold_kernel(const float *__restrict__ GW, const float *__restrict__ Gb,
+                                                   const double *__restrict__ L, int32_t n_slabs, int32_t c,
+                                                   int32_t dim, double *__restrict__ gW, double *__restrict__ gb,
+                                                   double *__restrict__ Lk) {
+  const int64_t cd = (int64_t)c * dim;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < cd) {
+    double s = 0.0;
+    for (int32_t sl = 0; sl < n_slabs; ++sl) s = s + (double)GW[sl * cd + i];
+    gW[i] = s;
+  } else if (i < cd + c) {
+    const int64_t k = i - cd;
+    double s = 0.0, l = 0.0;
+    for (int32_t sl = 0; sl < n_slabs; ++sl) {
+      s = s + (double)Gb[(int64_t)sl * c + k];
+      l = l + L[(int64_t)sl * c + k];
+    }
+    gb[k] = s;
+    Lk[k] = l;
+  }
+}
+
+__global__ void loss_kernel(const double *__restrict__ Lk, int32_t c, double *__restrict__ loss) {
+  double s = 0.0;
+  for (int32_t k = 0; k < c; ++k) s = s + Lk[k];
+  loss[0] = s;
+}
+
+bool sizes_ok(int64_t n, int32_t dim, int32_t c) {
+  return dim >= 1 && dim <= 1024 && n >= 0 && n < ((int64_t)1 << 31) && c >= 1 && c <= kMaxClasses;
+}
+
+bool workspace_ok(const void *ws, int64_t ws_bytes, int64_t n, int32_t dim, int32_t c) {
+  return ws && ((uintptr_t)ws & 15) == 0 && ws_bytes >= n2v_logreg_workspace_bytes(n, dim, c);
+}
+
+void launch_prep(const Plan &p, hipStream_t st, const float *W, int32_t c, int32_t dim, float *wpad) {
+  hipLaunchKernelGGL(prep_kernel, dim3((unsigned)((p.c_pad + 3) / 4)), dim3(256), 0, st, W, c, p.c_pad, dim, wpad);
+}
+
+template <int G>
+void launch_scores(bool vec, unsigned blocks, hipStream_t st, const float *X, int64_t n, int32_t dim,
+                   const float *wpad, const float *b, int32_t c, float *Z) {
+  if (vec)
+    hipLaunchKernelGGL((scores_kernel<G, true>), dim3(blocks), dim3(256), 0, st, X, n, dim, wpad, b, c, Z);
+  else
+    hipLaunchKernelGGL((scores_kernel<G, false>), dim3(blocks), dim3(256), 0, st, X, n, dim, wpad, b, c, Z);
+}
+
+template <int G>
+void launch_loss_grad(bool vec, const Plan &p, hipStream_t st, const float *X, const uint32_t *y_bits, int64_t n,
+                      int32_t dim, const float *wpad, const float *b, int32_t c, float *GW, float *Gb, double *L) {
+  if (vec)
+    hipLaunchKernelGGL((loss_grad_kernel<G, true>), dim3((unsigned)p.n_slabs), dim3(256), 0, st, X, y_bits, n, dim,
+                       wpad, b, c, GW, Gb, L, p.slab_rows);
+  else
+    hipLaunchKernelGGL((loss_grad_kernel<G, false>), dim3((unsigned)p.n_slabs), dim3(256), 0, st, X, y_bits, n, dim,
+                       wpad, b, c, GW, Gb, L, p.slab_rows);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t n2v_logreg_slab_rows(int64_t n, int32_t dim, int32_t c) {
+  if (!sizes_ok(n, dim, c)) return -1;
+  return plan_of(n, dim, c).slab_rows;
+}
+
+int64_t n2v_logreg_workspace_bytes(int64_t n, int32_t dim, int32_t c) {
+  if (!sizes_ok(n, dim, c)) return -1;
+  if (n == 0) return 0;
+  const Plan p = plan_of(n, dim, c);
+  return p.wpad_bytes + p.gw_bytes + p.gb_bytes + p.l_bytes + p.lk_bytes;
+}
+
+int n2v_logreg_scores(const float *X, int64_t n, int32_t dim, const float *W, const float *b, int32_t c,
+                      float *scores_out, void *workspace, int64_t workspace_bytes, void *stream) {
+  if (!sizes_ok(n, dim, c)) return N2V_EINVAL;
+  if (n == 0) return N2V_OK;
+  if (!X || !W || !b || !scores_out || !workspace_ok(workspace, workspace_bytes, n, dim, c)) return N2V_EINVAL;
+  const Plan p = plan_of(n, dim, c);
+  hipStream_t st = (hipStream_t)stream;
+  float *wpad = (float *)workspace;
+  launch_prep(p, st, W, c, dim, wpad);
+  N2V_HIP_CHECK(hipGetLastError());
+  const int64_t steps = (n + kStepRows - 1) / kStepRows;
+  const unsigned blocks = (unsigned)(steps < 4096 ? steps : 4096);
+  const bool vec = dim % 4 == 0 && ((uintptr_t)X & 15) == 0;
+  if (c <= 16)  // one group of 16 classes per tile; the bits do not depend on the tile
+    launch_scores<1>(vec, blocks, st, X, n, dim, wpad, b, c, scores_out);
+  else
+    launch_scores<4>(vec, blocks, st, X, n, dim, wpad, b, c, scores_out);
+  N2V_HIP_CHECK(hipGetLastError());
+  return N2V_OK;
+}
+
+int n2v_logreg_loss_grad(const float *X, const uint32_t *y_bits, int64_t n, int32_t dim, const float *W,
+                         const float *b, int32_t c, double *loss_out, double *grad_w_out, double *grad_b_out,
+                         void *workspace, int64_t workspace_bytes, void *stream) {
+  if (!sizes_ok(n, dim, c)) return N2V_EINVAL;
+  if (n == 0) return N2V_OK;
+  if (!X || !y_bits || !W || !b || !loss_out || !grad_w_out || !grad_b_out ||
+      !workspace_ok(workspace, workspace_bytes, n, dim, c))
+    return N2V_EINVAL;
+  const Plan p = plan_of(n, dim, c);
+  hipStream_t st = (hipStream_t)stream;
+  char *ws = (char *)workspace;
+  float *wpad = (float *)ws;
+  float *GW = (float *)(ws + p.wpad_bytes);
+  float *Gb = (float *)(ws + p.wpad_bytes + p.gw_bytes);
+  double *L = (double *)(ws + p.wpad_bytes + p.gw_bytes + p.gb_bytes);
+  double *Lk = (double *)(ws + p.wpad_bytes + p.gw_bytes + p.gb_bytes + p.l_bytes);
+  launch_prep(p, st, W, c, dim, wpad);
+  N2V_HIP_CHECK(hipGetLastError());
+  const bool vec = dim % 4 == 0 && ((uintptr_t)X & 15) == 0;
+  if (c <= 16)
+    launch_loss_grad<1>(vec, p, st, X, y_bits, n, dim, wpad, b, c, GW, Gb, L);
+  else
+    launch_loss_grad<4>(vec, p, st, X, y_bits, n, dim, wpad, b, c, GW, Gb, L);
+  N2V_HIP_CHECK(hipGetLastError());
+  const int64_t elems = (int64_t)c * dim + c;
+  hipLaunchKernelGGL(fold_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, GW, Gb, L, p.n_slabs, c,
+                     dim, grad_w_out, grad_b_out, Lk);
+  N2V_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(1), 0, st, Lk, c, loss_out);
+  N2V_HIP_CHECK(hipGetLastError());
+  return N2V_OK;
+}
+
+}  // extern "C"

@@ -353,6 +353,28 @@ class KeyedVectors:
             inv_norm = self._inv_norm[:n]
         return cluster.kmeans(X, k, metric=metric, inv_norm=inv_norm, **kw)
 
+    def logreg(self, Y, restrict_vocab: Optional[int] = None, **kw):
+        """one-vs-rest logistic regression of the vectors on the GPU (node2vec_amd.classify.fit, whose other
+        arguments pass through): a LogRegResult; row i of Y (bool or 0/1 [n, c]) holds the labels of token
+        index2word[i].  restrict_vocab: only the first rows are used."""
+        from node2vec_amd import classify
+
+        n = len(self)
+        if restrict_vocab is not None:
+            if int(restrict_vocab) < 0:
+                raise ValueError("restrict_vocab must be >= 0")
+            n = min(n, int(restrict_vocab))
+        Y = torch.as_tensor(Y)
+        if Y.ndim != 2 or Y.shape[0] < n:
+            raise ValueError(f"Y must hold one row of labels per vector: [{n}, c]")
+        return classify.fit(self._device_vectors()[:n], Y[:n], **kw)
+
+    def label_scores(self, result) -> torch.Tensor:
+        """fp32 [n, c] on the device: the decision function of a LogRegResult for every vector"""
+        from node2vec_amd import classify
+
+        return classify.decision_function(self._device_vectors(), result.W, result.b)
+
     @classmethod
     def load_word2vec_format(cls, fname: str) -> "KeyedVectors":
         with open(fname) as f:
@@ -461,7 +483,50 @@ class _ClusterQueries:
         return self.clusters
 
 
-class Node2VecHIP(Node2VecBase, _PairQueries, _ClusterQueries):
+class _LabelQueries:
+    """classify() of a fitted model: what Node2VecHIP and Node2VecSpark share."""
+
+    model = None
+    name_id = None
+    classifier = None
+    label_f1 = None
+
+    def classify(self, df_labels: pd.DataFrame, train_fraction: float = 0.5, seed: int = 0, **kw) -> pd.DataFrame:
+        """The node2vec paper's multi-label classification (section 4.3): one-vs-rest logistic regression on
+        train_fraction of the vocabulary vertices (node2vec_amd.classify.evaluate, whose other arguments pass
+        through), df_labels holding one ["id", "label"] row per (vertex, label).  Returns one row per (vertex,
+        class), in vocabulary order: ["id" | "name", "label", "score", "predicted", "train"].  Names go through
+        name_id as in cluster().  The LogRegResult is kept as self.classifier, the F1 of the held-out vertices as
+        self.label_f1."""
+        if self.model is None:
+            raise ValueError("Model is not available. Please run fit()")
+        from node2vec_amd import classify
+
+        wv = self.model.wv
+        ids = wv.ids if wv.ids is not None else np.array([int(t) for t in wv.index2word], dtype=np.int64)
+        names = None
+        if self.name_id is not None:
+            names = self.name_id.drop_duplicates("id", keep="last").set_index("id")["name"]
+            missing = ~pd.Index(ids).isin(names.index)
+            if missing.any():
+                raise KeyError(int(ids[missing][0]))
+        Y, classes = classify.labels_from_frame(df_labels, ids)
+        top = kw.pop("top", True)
+        X = wv._device_vectors()
+        self.classifier, self.label_f1 = classify.evaluate(X, Y, train_fraction, seed, top=top, **kw)
+        scores = wv.label_scores(self.classifier)
+        truth = Y.to(scores.device)
+        pred = classify.predict_top(scores, truth.sum(1)) if top else classify.predict(scores)
+        train = np.zeros(len(ids), dtype=bool)
+        train[classify.split_rows(len(ids), train_fraction, seed)[0]] = True
+        c = len(classes)
+        who = ids if names is None else names.reindex(ids).to_numpy()
+        return pd.DataFrame({("id" if names is None else "name"): np.repeat(who, c), "label": np.tile(classes, len(ids)),
+                             "score": scores[:, :c].cpu().numpy().reshape(-1),
+                             "predicted": pred[:, :c].cpu().numpy().reshape(-1), "train": np.repeat(train, c)})
+
+
+class Node2VecHIP(Node2VecBase, _PairQueries, _ClusterQueries, _LabelQueries):
     """Drop-in for Node2VecGensim (embedding.py:70-178) on one MI355X."""
 
     def __init__(
@@ -708,7 +773,7 @@ HIP_HS_PARAMS: Dict[str, Any] = {
 }
 
 
-class Node2VecSpark(Node2VecBase, _PairQueries, _ClusterQueries):
+class Node2VecSpark(Node2VecBase, _PairQueries, _ClusterQueries, _LabelQueries):
     """Drop-in for the reference's Node2VecSpark (embedding.py:182-285) on one MI355X: skip-gram with
     hierarchical softmax, what Spark ML's Word2Vec trains (node2vec_amd/hs.py, csrc/n2v_hs.hip).
 
