@@ -14,7 +14,7 @@ from typing import Callable, Dict, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from node2vec_amd import _lib, similarity
+from node2vec_amd import _dense, _lib
 
 MAX_CLASSES = 1024
 ARMIJO_C1 = 1e-4
@@ -32,12 +32,6 @@ class LogRegResult(NamedTuple):
     reason: str          # "gradient" | "max_iter" | "line_search"
 
 
-def _shape(X) -> Tuple[int, int]:
-    if not isinstance(X, torch.Tensor) or X.ndim != 2:
-        raise ValueError("X must be a 2-D tensor on a HIP device")
-    return int(X.shape[0]), int(X.shape[1])
-
-
 def _params(W, b, dim: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
     if not isinstance(W, torch.Tensor) or W.ndim != 2 or W.shape[1] != dim:
         raise ValueError(f"W must be a [c, {dim}] tensor")
@@ -50,9 +44,8 @@ def _params(W, b, dim: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
             b.to(device=device, dtype=torch.float32).contiguous())
 
 
-def _workspace(n: int, dim: int, c: int, device) -> torch.Tensor:
-    need = int(_lib.load().n2v_logreg_workspace_bytes(n, dim, c))
-    return torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+def alloc_workspace(n: int, dim: int, c: int, device) -> torch.Tensor:
+    return _dense.workspace(_lib.load().n2v_logreg_workspace_bytes, n, dim, c, device=device)
 
 
 def slab_rows(n: int, dim: int, c: int) -> int:
@@ -98,13 +91,13 @@ def labels_from_frame(df, ids) -> Tuple[torch.Tensor, np.ndarray]:
 
 def decision_function(X: torch.Tensor, W: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """fp32 [n, c]: z[r][k] = dot(W_k, x_r) + b[k] (n2v_logreg_scores)"""
-    n, dim = _shape(X)
-    X = similarity._matrix(X)
+    n, dim = _dense.shape(X)
+    X = _dense.matrix(X)
     W, b = _params(W, b, dim, X.device)
     c = W.shape[0]
     Z = torch.empty((n, c), dtype=torch.float32, device=X.device)
     with torch.cuda.device(X.device):
-        ws = _workspace(n, dim, c, X.device)
+        ws = alloc_workspace(n, dim, c, X.device)
         _lib.check(_lib.load().n2v_logreg_scores(X.data_ptr(), n, dim, W.data_ptr(), b.data_ptr(), c, Z.data_ptr(),
                                                  ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
                    "n2v_logreg_scores")
@@ -113,8 +106,8 @@ def decision_function(X: torch.Tensor, W: torch.Tensor, b: torch.Tensor) -> torc
 
 def _loss_grad_flat(X, y_bits, W, b, workspace=None) -> torch.Tensor:
     """float64 [1 + c dim + c] on the device: loss, gW, gb"""
-    n, dim = _shape(X)
-    X = similarity._matrix(X)
+    n, dim = _dense.shape(X)
+    X = _dense.matrix(X)
     W, b = _params(W, b, dim, X.device)
     c = W.shape[0]
     if not isinstance(y_bits, torch.Tensor) or y_bits.dtype != torch.int32 or \
@@ -123,7 +116,7 @@ def _loss_grad_flat(X, y_bits, W, b, workspace=None) -> torch.Tensor:
     y_bits = y_bits.to(X.device).contiguous()
     out = torch.zeros(1 + c * dim + c, dtype=torch.float64, device=X.device)
     with torch.cuda.device(X.device):
-        ws = workspace if workspace is not None else _workspace(n, dim, c, X.device)
+        ws = workspace if workspace is not None else alloc_workspace(n, dim, c, X.device)
         _lib.check(_lib.load().n2v_logreg_loss_grad(X.data_ptr(), y_bits.data_ptr(), n, dim, W.data_ptr(),
                                                     b.data_ptr(), c, out.data_ptr(), out[1:].data_ptr(),
                                                     out[1 + c * dim:].data_ptr(), ws.data_ptr(), ws.numel(),
@@ -169,7 +162,7 @@ def fit(X: torch.Tensor, Y: torch.Tensor, C: float = 1.0, max_iter: int = 100, t
     ("max_iter") or when the line search fails ("line_search").  One evaluation is one pass over X and one
     synchronisation (the copy of the [c, dim + 1] sums to the host).  X holding a non-finite value is a ValueError.
     loss_grad_fn(W, b) -> (loss, gW, gb) replaces the kernel (host tensors in and out), for tests."""
-    n, dim = _shape(X)
+    n, dim = _dense.shape(X)
     if not isinstance(Y, torch.Tensor) or Y.ndim != 2 or Y.shape[0] != n:
         raise ValueError(f"Y must be a [{n}, c] tensor")
     c = int(Y.shape[1])
@@ -178,9 +171,9 @@ def fit(X: torch.Tensor, Y: torch.Tensor, C: float = 1.0, max_iter: int = 100, t
     if not float(C) > 0.0 or int(max_iter) < 1 or not float(tol) >= 0.0 or int(history) < 1 or n < 1:
         raise ValueError("C must be > 0, max_iter, history and n >= 1, tol >= 0")
     if loss_grad_fn is None:
-        X = similarity._matrix(X)
+        X = _dense.matrix(X)
         y_bits = pack_labels(Y.to(X.device))
-        ws = _workspace(n, dim, c, X.device)
+        ws = alloc_workspace(n, dim, c, X.device)
 
         def loss_grad_fn(W, b):  # host parameters in, host sums out: the copy back is the one synchronisation
             flat = _loss_grad_flat(X, y_bits, W.to(X.device), b.to(X.device), ws).cpu()
@@ -284,8 +277,8 @@ def evaluate(X: torch.Tensor, Y: torch.Tensor, train_fraction: float = 0.5, seed
     """The paper's protocol -> (LogRegResult, F1 dictionary of the held-out rows); the rows are split_rows(n,
     train_fraction, seed).  X[train] is gathered once into a contiguous copy.  top: predict_top with every test
     row's true number of labels; else     predict at 0."""
-    n, _ = _shape(X)
-    X = similarity._matrix(X)
+    n, _ = _dense.shape(X)
+    X = _dense.matrix(X)
     Y = Y.to(X.device)
     train, test = split_rows(n, train_fraction, seed)
     tr, te = torch.from_numpy(train).to(X.device), torch.from_numpy(test).to(X.device)

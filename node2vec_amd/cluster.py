@@ -16,7 +16,7 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from node2vec_amd import _lib, similarity
+from node2vec_amd import _dense, _lib, similarity
 
 METRICS = {"euclidean": _lib.KMEANS_EUCLIDEAN, "cosine": _lib.KMEANS_COSINE}
 INITS = ("k-means++", "random")
@@ -34,24 +34,18 @@ class KMeansResult(NamedTuple):
     n_unassigned: int
 
 
-def _check_metric(metric: str) -> None:
+def check_metric(metric: str) -> None:
     if metric not in METRICS:
         raise ValueError(f"metric {metric!r}: " + " | ".join(METRICS))
 
 
-def _check_k(k, n: Optional[int] = None) -> int:
+def check_k(k, n: Optional[int] = None) -> int:
     k = int(k)
     if k < 1 or k > MAX_K:
         raise ValueError(f"k = {k} outside [1, {MAX_K}]")
     if n is not None and k > n:
         raise ValueError(f"k = {k} clusters of n = {n} rows")
     return k
-
-
-def _shape(X) -> Tuple[int, int]:
-    if not isinstance(X, torch.Tensor) or X.ndim != 2:
-        raise ValueError("X must be a 2-D tensor on a HIP device")
-    return int(X.shape[0]), int(X.shape[1])
 
 
 def _norms(X: torch.Tensor, metric: str, inv_norm: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -73,13 +67,11 @@ def _centroids(C, k: Optional[int], dim: int) -> torch.Tensor:
     return C
 
 
-def _workspace(n: int, dim: int, k: int, device) -> torch.Tensor:
-    need = int(_lib.load().n2v_kmeans_workspace_bytes(n, dim, k))
-    return torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+def alloc_workspace(n: int, dim: int, k: int, device) -> torch.Tensor:
+    return _dense.workspace(_lib.load().n2v_kmeans_workspace_bytes, n, dim, k, device=device)
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+_workspace = alloc_workspace  # the name callers used before it became public
 
 
 def _unit(C: torch.Tensor) -> torch.Tensor:
@@ -96,20 +88,20 @@ def assign(X: torch.Tensor, centroids: torch.Tensor, metric: str = "euclidean",
     """(labels int32 [n], dist fp32 [n]): the nearest centroid of every row (ties: the lowest index) and the
     distance to it -- squared Euclidean, or 1 - cosine against UNIT centroids (init_centroids and update return
     such).  inv_norm: similarity.inv_norms(X) for cosine, computed when not given."""
-    _check_metric(metric)
-    n, dim = _shape(X)
+    check_metric(metric)
+    n, dim = _dense.shape(X)
     _centroids(centroids, None, dim)
-    X = similarity._matrix(X)
+    X = _dense.matrix(X)
     C = centroids.to(device=X.device, dtype=torch.float32).contiguous()
     k = C.shape[0]
     norms = _norms(X, metric, inv_norm)
     labels = torch.empty(n, dtype=torch.int32, device=X.device)
     dist = torch.empty(n, dtype=torch.float32, device=X.device)
     with torch.cuda.device(X.device):
-        ws = _workspace(n, dim, k, X.device)
-        _lib.check(_lib.load().n2v_kmeans_assign(X.data_ptr(), _ptr(norms), n, dim, C.data_ptr(), k, METRICS[metric],
-                                                 labels.data_ptr(), dist.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                 _lib.current_stream_ptr()), "n2v_kmeans_assign")
+        ws = alloc_workspace(n, dim, k, X.device)
+        _lib.check(_lib.load().n2v_kmeans_assign(X.data_ptr(), _dense.ptr(norms), n, dim, C.data_ptr(), k,
+                                                 METRICS[metric], labels.data_ptr(), dist.data_ptr(), ws.data_ptr(),
+                                                 ws.numel(), _lib.current_stream_ptr()), "n2v_kmeans_assign")
     return labels, dist
 
 
@@ -118,21 +110,21 @@ def update(X: torch.Tensor, labels: torch.Tensor, k: int, metric: str, prev_cent
     """(centroids fp32 [k, dim], counts int64 [k]): the mean of every cluster's rows (cosine: the unit vector of the
     sum of their unit vectors); an empty cluster keeps its row of prev_centroids.  A label outside [0, k) joins no
     cluster."""
-    _check_metric(metric)
-    n, dim = _shape(X)
-    k = _check_k(k)
+    check_metric(metric)
+    n, dim = _dense.shape(X)
+    k = check_k(k)
     _centroids(prev_centroids, k, dim)
     if not isinstance(labels, torch.Tensor) or labels.ndim != 1 or labels.shape[0] != n:
         raise ValueError(f"labels must be a [{n}] tensor")
-    X = similarity._matrix(X)
+    X = _dense.matrix(X)
     prev = prev_centroids.to(device=X.device, dtype=torch.float32).contiguous()
     labels = labels.to(device=X.device, dtype=torch.int32).contiguous()
     norms = _norms(X, metric, inv_norm)
     out = prev.clone()
     counts = torch.zeros(k, dtype=torch.int64, device=X.device)
     with torch.cuda.device(X.device):
-        ws = _workspace(n, dim, k, X.device)
-        _lib.check(_lib.load().n2v_kmeans_update(X.data_ptr(), _ptr(norms), n, dim, labels.data_ptr(), k,
+        ws = alloc_workspace(n, dim, k, X.device)
+        _lib.check(_lib.load().n2v_kmeans_update(X.data_ptr(), _dense.ptr(norms), n, dim, labels.data_ptr(), k,
                                                  METRICS[metric], prev.data_ptr(), out.data_ptr(), counts.data_ptr(),
                                                  ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
                    "n2v_kmeans_update")
@@ -160,14 +152,14 @@ def init_centroids(X: torch.Tensor, k: int, metric: str = "euclidean", seed: int
     drawn with probability proportional to the distance to the nearest centre chosen so far (one assign pass with
     k = 1 per centre); or a [k, dim] tensor, used as it is (normalised for cosine).  The same seed gives the same
     centres."""
-    _check_metric(metric)
-    n, dim = _shape(X)
-    k = _check_k(k, n)
+    check_metric(metric)
+    n, dim = _dense.shape(X)
+    k = check_k(k, n)
     if isinstance(init, torch.Tensor):
         _centroids(init, k, dim)
     elif init not in INITS:
         raise ValueError(f"init {init!r}: " + " | ".join(INITS) + " | a [k, dim] tensor")
-    X = similarity._matrix(X)
+    X = _dense.matrix(X)
     unit = _unit if metric == "cosine" else (lambda C: C)
     if isinstance(init, torch.Tensor):
         return unit(init.to(device=X.device, dtype=torch.float32).contiguous().clone())
@@ -196,10 +188,10 @@ def _lloyd(X, norms, C, metric, max_iter, tol) -> KMeansResult:
     nxt = torch.empty_like(C)
     counts = torch.zeros(k, dtype=torch.int64, device=X.device)
     stats = torch.zeros(2, dtype=torch.int64, device=X.device)
-    ws = _workspace(n, dim, k, X.device)
+    ws = alloc_workspace(n, dim, k, X.device)
     n_iter, settled, converged = 0, False, False
     for n_iter in range(1, max_iter + 1):
-        _lib.check(L.n2v_kmeans_step(X.data_ptr(), _ptr(norms), n, dim, C.data_ptr(), k, METRICS[metric],
+        _lib.check(L.n2v_kmeans_step(X.data_ptr(), _dense.ptr(norms), n, dim, C.data_ptr(), k, METRICS[metric],
                                      labels.data_ptr(), dist.data_ptr(), nxt.data_ptr(), counts.data_ptr(),
                                      stats.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
                    "n2v_kmeans_step")
@@ -213,7 +205,7 @@ def _lloyd(X, norms, C, metric, max_iter, tol) -> KMeansResult:
             converged = True
             break
     if not settled:  # labels and distances against the centroids that are returned
-        _lib.check(L.n2v_kmeans_assign(X.data_ptr(), _ptr(norms), n, dim, C.data_ptr(), k, METRICS[metric],
+        _lib.check(L.n2v_kmeans_assign(X.data_ptr(), _dense.ptr(norms), n, dim, C.data_ptr(), k, METRICS[metric],
                                        labels.data_ptr(), dist.data_ptr(), ws.data_ptr(), ws.numel(),
                                        _lib.current_stream_ptr()), "n2v_kmeans_assign")
     live = labels >= 0
@@ -230,16 +222,16 @@ def kmeans(X: torch.Tensor, k: int, metric: str = "euclidean", init="k-means++",
     centres is <= tol (converged), or after max_iter iterations.  Unless it stopped on unchanged labels, one more
     assignment makes labels and dist those of the returned centroids.  n_init > 1: seeds seed, seed + 1, ...; the
     run of lowest inertia is returned (ties: the first).  One host synchronisation per iteration."""
-    _check_metric(metric)
-    n, dim = _shape(X)
-    k = _check_k(k, n)
+    check_metric(metric)
+    n, dim = _dense.shape(X)
+    k = check_k(k, n)
     if isinstance(init, torch.Tensor):
         _centroids(init, k, dim)
     elif init not in INITS:
         raise ValueError(f"init {init!r}: " + " | ".join(INITS) + " | a [k, dim] tensor")
     if int(n_init) < 1 or int(max_iter) < 1 or not float(tol) >= 0.0:
         raise ValueError("n_init and max_iter must be >= 1 and tol >= 0")
-    X = similarity._matrix(X)
+    X = _dense.matrix(X)
     norms = _norms(X, metric, inv_norm)
     best = None
     with torch.cuda.device(X.device):

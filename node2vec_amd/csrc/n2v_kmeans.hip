@@ -22,43 +22,28 @@
 
 namespace {
 
-constexpr int kStepRows = 64;                   // rows per block step: 16 per wave, 4 waves
-constexpr int kMaxSlabs = 2048;                 // blocks of the launch (8 per CU)
-constexpr int64_t kPartialsCap = 512ll << 20;   // bytes of slab partials at most
+constexpr int kStepRows = kSlabStepRows;
 constexpr int kModeAssign = 1, kModeUpdate = 2;
 
+// the slabs, and the workspace `ws` laid out (ws null: only `bytes` means anything): the centroids padded to
+// [k_pad][dim_pad], their sums of squares, the slabs' partial sums
 struct Plan {
-  int64_t slab_rows, k_pad, cpad_bytes, cn_bytes, part_bytes;
-  int32_t n_slabs;
+  SlabPlan slabs;
+  int64_t k_pad, bytes;
+  float *cpad, *cn, *part;
 };
 
-Plan plan_of(int64_t n, int32_t dim, int32_t k) {
+Plan plan_of(int64_t n, int32_t dim, int32_t k, void *ws) {
   Plan p{};
   const int64_t per_slab = (int64_t)k * dim * 4;
-  int64_t most = kPartialsCap / per_slab;  // >= 128: per_slab <= 4 MiB
-  if (most > kMaxSlabs) most = kMaxSlabs;
-  const int64_t share = (n + most - 1) / most;
-  p.slab_rows = round_up(share < 1 ? 1 : share, kStepRows);
-  p.n_slabs = (int32_t)((n + p.slab_rows - 1) / p.slab_rows);
+  p.slabs = slab_plan(n, per_slab);
   p.k_pad = round_up(k, 64);
-  p.cpad_bytes = round_up(p.k_pad * dim_pad_of(dim) * 4, 256);
-  p.cn_bytes = round_up(p.k_pad * 4, 256);
-  p.part_bytes = round_up((int64_t)p.n_slabs * per_slab, 256);
+  Carver carve(ws);
+  p.cpad = carve.take<float>(p.k_pad * dim_pad_of(dim) * 4);
+  p.cn = carve.take<float>(p.k_pad * 4);
+  p.part = carve.take<float>(p.slabs.n_slabs * per_slab);
+  p.bytes = carve.used;
   return p;
-}
-
-// the centroids padded to [k_pad][dim_pad] with zeros, and their sums of squares; one wave per padded row
-__global__ __launch_bounds__(256) void prep_kernel(const float *__restrict__ centroids, int32_t k, int64_t k_pad,
-                                                   int32_t dim, float *__restrict__ cpad, float *__restrict__ cn) {
-  const int lane = threadIdx.x & 63;
-  const int32_t dp = dim_pad_of(dim);
-  const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (c >= k_pad) return;
-  const bool live = c < k;
-  const float *v = centroids + (live ? c : 0) * dim;
-  for (int d = lane; d < dp; d += 64) cpad[c * dp + d] = (live && d < dim) ? v[d] : 0.f;
-  const float s = wave_sumsq(v, dim, lane);
-  if (lane == 0) cn[c] = live ? s : 0.f;
 }
 
 // Block s owns slab s: rows [s slab_rows, ..).  mode: kModeAssign scores and writes labels / dist (and, with
@@ -213,51 +198,30 @@ __global__ __launch_bounds__(64) void finish_kernel(const float *__restrict__ pa
 }
 
 bool sizes_ok(int64_t n, int32_t dim, int32_t k, int32_t metric) {
-  return dim >= 1 && dim <= 1024 && n >= 0 && n < ((int64_t)1 << 31) && k >= 1 && k <= 1024 &&
-         (metric == N2V_KMEANS_EUCLIDEAN || metric == N2V_KMEANS_COSINE);
+  return matrix_ok(n, dim) && k >= 1 && k <= 1024 && (metric == N2V_KMEANS_EUCLIDEAN || metric == N2V_KMEANS_COSINE);
 }
 
-bool workspace_ok(const void *ws, int64_t ws_bytes, int64_t n, int32_t dim, int32_t k) {
-  return ws && ((uintptr_t)ws & 15) == 0 && ws_bytes >= n2v_kmeans_workspace_bytes(n, dim, k);
-}
-
-template <int G>
-void launch_lloyd(bool vec, const Plan &p, hipStream_t st, const float *X, const float *inv_norm, int64_t n,
-                  int32_t dim, const float *cpad, const float *cn, int32_t k, int32_t metric, int32_t mode,
-                  int32_t *labels, float *dist, float *part, unsigned long long *counts, unsigned long long *stats) {
-  if (vec)
-    hipLaunchKernelGGL((lloyd_kernel<G, true>), dim3((unsigned)p.n_slabs), dim3(256), 0, st, X, inv_norm, n, dim,
-                       cpad, cn, k, metric, mode, labels, dist, part, counts, stats, p.slab_rows);
-  else
-    hipLaunchKernelGGL((lloyd_kernel<G, false>), dim3((unsigned)p.n_slabs), dim3(256), 0, st, X, inv_norm, n, dim,
-                       cpad, cn, k, metric, mode, labels, dist, part, counts, stats, p.slab_rows);
-}
-
-// prep (when assigning), the slab launch, finish (when updating); everything was validated by the caller
+// prep (when assigning), the slab launch, finish (when updating); the workspace is checked here, everything else
+// was validated by the caller
 int run(int32_t mode, const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *centroids_in,
         int32_t k, int32_t metric, int32_t *labels, float *dist, const float *prev, float *centroids_out,
-        int64_t *counts_out, int64_t *stats_out, void *ws, hipStream_t st) {
-  const Plan p = plan_of(n, dim, k);
-  float *cpad = (float *)ws;
-  float *cn = (float *)((char *)ws + p.cpad_bytes);
-  float *part = (float *)((char *)ws + p.cpad_bytes + p.cn_bytes);
+        int64_t *counts_out, int64_t *stats_out, void *ws, int64_t ws_bytes, hipStream_t st) {
+  const Plan p = plan_of(n, dim, k, ws);
+  if (!workspace_ok(ws, ws_bytes, p.bytes)) return N2V_EINVAL;
   if (mode & kModeAssign) {
-    hipLaunchKernelGGL(prep_kernel, dim3((unsigned)((p.k_pad + 3) / 4)), dim3(256), 0, st, centroids_in, k, p.k_pad,
-                       dim, cpad, cn);
+    launch_pad_rows(st, centroids_in, k, p.k_pad, dim, p.cpad, p.cn);
     N2V_HIP_CHECK(hipGetLastError());
   }
   if (mode & kModeUpdate) N2V_HIP_CHECK(hipMemsetAsync(counts_out, 0, (size_t)k * 8, st));
   if (stats_out) N2V_HIP_CHECK(hipMemsetAsync(stats_out, 0, 16, st));
-  const bool vec = dim % 4 == 0 && ((uintptr_t)X & 15) == 0;
-  if (k <= 16)  // one group of 16 centroids per tile; the bits do not depend on the tile
-    launch_lloyd<1>(vec, p, st, X, inv_norm, n, dim, cpad, cn, k, metric, mode, labels, dist, part,
-                    (unsigned long long *)counts_out, (unsigned long long *)stats_out);
-  else
-    launch_lloyd<4>(vec, p, st, X, inv_norm, n, dim, cpad, cn, k, metric, mode, labels, dist, part,
-                    (unsigned long long *)counts_out, (unsigned long long *)stats_out);
+  with_tile(k, vec_ok(dim, X), [&](auto G, auto VEC) {
+    hipLaunchKernelGGL((lloyd_kernel<G, VEC>), dim3((unsigned)p.slabs.n_slabs), dim3(256), 0, st, X, inv_norm, n, dim,
+                       p.cpad, p.cn, k, metric, mode, labels, dist, p.part, (unsigned long long *)counts_out,
+                       (unsigned long long *)stats_out, p.slabs.slab_rows);
+  });
   N2V_HIP_CHECK(hipGetLastError());
   if (mode & kModeUpdate) {
-    hipLaunchKernelGGL(finish_kernel, dim3((unsigned)k), dim3(64), 0, st, part, p.n_slabs, k, dim, metric,
+    hipLaunchKernelGGL(finish_kernel, dim3((unsigned)k), dim3(64), 0, st, p.part, p.slabs.n_slabs, k, dim, metric,
                        (const unsigned long long *)counts_out, prev, centroids_out);
     N2V_HIP_CHECK(hipGetLastError());
   }
@@ -270,14 +234,12 @@ extern "C" {
 
 int64_t n2v_kmeans_slab_rows(int64_t n, int32_t dim, int32_t k) {
   if (!sizes_ok(n, dim, k, N2V_KMEANS_EUCLIDEAN)) return -1;
-  return plan_of(n, dim, k).slab_rows;
+  return plan_of(n, dim, k, nullptr).slabs.slab_rows;
 }
 
 int64_t n2v_kmeans_workspace_bytes(int64_t n, int32_t dim, int32_t k) {
   if (!sizes_ok(n, dim, k, N2V_KMEANS_EUCLIDEAN)) return -1;
-  if (n == 0) return 0;
-  const Plan p = plan_of(n, dim, k);
-  return p.cpad_bytes + p.cn_bytes + p.part_bytes;
+  return n == 0 ? 0 : plan_of(n, dim, k, nullptr).bytes;
 }
 
 int n2v_kmeans_assign(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *centroids,
@@ -286,9 +248,9 @@ int n2v_kmeans_assign(const float *X, const float *inv_norm, int64_t n, int32_t 
   if (!sizes_ok(n, dim, k, metric)) return N2V_EINVAL;
   if (metric == N2V_KMEANS_COSINE && !inv_norm) return N2V_EINVAL;
   if (n == 0) return N2V_OK;
-  if (!X || !centroids || !labels_out || !workspace_ok(workspace, workspace_bytes, n, dim, k)) return N2V_EINVAL;
+  if (!X || !centroids || !labels_out) return N2V_EINVAL;
   return run(kModeAssign, X, inv_norm, n, dim, centroids, k, metric, labels_out, dist_out, nullptr, nullptr,
-             nullptr, nullptr, workspace, (hipStream_t)stream);
+             nullptr, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int n2v_kmeans_update(const float *X, const float *inv_norm, int64_t n, int32_t dim, const int32_t *labels,
@@ -297,11 +259,10 @@ int n2v_kmeans_update(const float *X, const float *inv_norm, int64_t n, int32_t 
   if (!sizes_ok(n, dim, k, metric)) return N2V_EINVAL;
   if (metric == N2V_KMEANS_COSINE && !inv_norm) return N2V_EINVAL;
   if (n == 0) return N2V_OK;
-  if (!X || !labels || !prev_centroids || !centroids_out || !counts_out || centroids_out == prev_centroids ||
-      !workspace_ok(workspace, workspace_bytes, n, dim, k))
+  if (!X || !labels || !prev_centroids || !centroids_out || !counts_out || centroids_out == prev_centroids)
     return N2V_EINVAL;
   return run(kModeUpdate, X, inv_norm, n, dim, nullptr, k, metric, const_cast<int32_t *>(labels), nullptr,
-             prev_centroids, centroids_out, counts_out, nullptr, workspace, (hipStream_t)stream);
+             prev_centroids, centroids_out, counts_out, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int n2v_kmeans_step(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *centroids_in,
@@ -312,11 +273,10 @@ int n2v_kmeans_step(const float *X, const float *inv_norm, int64_t n, int32_t di
   if (metric == N2V_KMEANS_COSINE && !inv_norm) return N2V_EINVAL;
   if (n == 0) return N2V_OK;
   if (!X || !centroids_in || !labels_inout || !centroids_out || !counts_out || !stats_out ||
-      centroids_out == centroids_in || !workspace_ok(workspace, workspace_bytes, n, dim, k))
+      centroids_out == centroids_in)
     return N2V_EINVAL;
-  if (n == 0) return N2V_OK;
   return run(kModeAssign | kModeUpdate, X, inv_norm, n, dim, centroids_in, k, metric, labels_inout, dist_out,
-             centroids_in, centroids_out, counts_out, stats_out, workspace, (hipStream_t)stream);
+             centroids_in, centroids_out, counts_out, stats_out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

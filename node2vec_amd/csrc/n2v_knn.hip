@@ -246,15 +246,23 @@ __global__ __launch_bounds__(256) void merge_kernel(float *__restrict__ s0, int3
   }
 }
 
-// the launch shape of n2v_knn_topk: query tile, LDS buffer, chunks
+// q_hat, the first piece of every workspace
+float *take_qhat(Carver &carve, int32_t dim, int64_t nq) {
+  return carve.take<float>(nq_pad_of(nq) * dim_pad_of(dim) * 4);
+}
+
+// the launch shape of n2v_knn_topk: query tile, LDS buffer, chunks; and the workspace `ws` laid out (ws null: only
+// `bytes` means anything): q_hat, then the two halves (scores, rows) of the chunk lists that the merge ping-pongs
 struct TopkPlan {
   int variant;  // 0: G 4 / CAP 256, 1: G 2 / CAP 512, 2: G 1 / CAP 1024, 3: G 1 (8 queries kept) / CAP 2048
   int qt;       // queries per block
   int32_t n_chunks;
-  int64_t chunk_rows, nq_pad, qhat_bytes, part_bytes;
+  int64_t chunk_rows, bytes;
+  float *qhat, *s0, *s1;
+  int32_t *r0, *r1;
 };
 
-TopkPlan plan_topk(int64_t n, int32_t dim, int64_t nq, int32_t k) {
+TopkPlan plan_topk(int64_t n, int32_t dim, int64_t nq, int32_t k, void *ws) {
   TopkPlan p{};
   if (k <= 128 && nq > 32) p.variant = 0, p.qt = 64;
   else if (k <= 384 && nq > 16) p.variant = 1, p.qt = 32;
@@ -270,24 +278,28 @@ TopkPlan plan_topk(int64_t n, int32_t dim, int64_t nq, int32_t k) {
   p.chunk_rows = round_up((n + chunks - 1) / chunks, kStepRows);
   p.n_chunks = (int32_t)((n + p.chunk_rows - 1) / p.chunk_rows);
   if (p.n_chunks < 1) p.n_chunks = 1;
-  p.nq_pad = nq_pad_of(nq);
-  p.qhat_bytes = round_up(p.nq_pad * dim_pad_of(dim) * 4, 256);
-  p.part_bytes = round_up(nq * (int64_t)p.n_chunks * k * 4, 256);  // one of the four part arrays
+  const int64_t part = nq * (int64_t)p.n_chunks * k * 4;
+  Carver carve(ws);
+  p.qhat = take_qhat(carve, dim, nq);
+  p.s0 = carve.take<float>(part);
+  p.r0 = carve.take<int32_t>(part);
+  p.s1 = carve.take<float>(part);
+  p.r1 = carve.take<int32_t>(part);
+  p.bytes = carve.used;
   return p;
 }
 
-int64_t qhat_only_bytes(int32_t dim, int64_t nq) { return round_up(nq_pad_of(nq) * dim_pad_of(dim) * 4, 256); }
-
 bool args_ok(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *queries,
              const int64_t *query_rows, int64_t nq) {
-  if (dim < 1 || dim > 1024 || n < 0 || n >= ((int64_t)1 << 31) || nq < 0) return false;
+  if (!matrix_ok(n, dim) || nq < 0) return false;
   if ((queries == nullptr) == (query_rows == nullptr)) return false;
   if (!X || !inv_norm) return false;
   return true;
 }
 
 int launch_queries(const float *X, const float *inv_norm, int32_t dim, const float *queries,
-                   const int64_t *query_rows, int64_t nq, int64_t nq_pad, float *qhat, hipStream_t st) {
+                   const int64_t *query_rows, int64_t nq, float *qhat, hipStream_t st) {
+  const int64_t nq_pad = nq_pad_of(nq);
   hipLaunchKernelGGL(queries_kernel, dim3((unsigned)((nq_pad + 3) / 4)), dim3(256), 0, st, X, inv_norm, dim,
                      queries, query_rows, nq, nq_pad, qhat);
   N2V_HIP_CHECK(hipGetLastError());
@@ -295,27 +307,21 @@ int launch_queries(const float *X, const float *inv_norm, int32_t dim, const flo
 }
 
 template <int G, int QACT, int CAP>
-int launch_topk(bool vec, const TopkPlan &p, const float *X, const float *inv_norm, int64_t n, int32_t dim,
-                const float *qhat, int64_t nq, int32_t k, float *ps, int32_t *pr, hipStream_t st) {
+void launch_topk(const TopkPlan &p, const float *X, const float *inv_norm, int64_t n, int32_t dim, int64_t nq,
+                 int32_t k, hipStream_t st) {
   const dim3 grid((unsigned)((nq + QACT - 1) / QACT), (unsigned)p.n_chunks);
-  if (vec)
-    hipLaunchKernelGGL((topk_chunk_kernel<G, QACT, CAP, true>), grid, dim3(kWaves * 64), 0, st, X, inv_norm, n,
-                       dim, qhat, nq, k, p.chunk_rows, p.n_chunks, ps, pr);
-  else
-    hipLaunchKernelGGL((topk_chunk_kernel<G, QACT, CAP, false>), grid, dim3(kWaves * 64), 0, st, X, inv_norm, n,
-                       dim, qhat, nq, k, p.chunk_rows, p.n_chunks, ps, pr);
-  N2V_HIP_CHECK(hipGetLastError());
-  return N2V_OK;
+  with_bool(vec_ok(dim, X), [&](auto VEC) {
+    hipLaunchKernelGGL((topk_chunk_kernel<G, QACT, CAP, VEC>), grid, dim3(kWaves * 64), 0, st, X, inv_norm, n, dim,
+                       p.qhat, nq, k, p.chunk_rows, p.n_chunks, p.s0, p.r0);
+  });
 }
-
-bool vec_ok(const float *X, int32_t dim) { return dim % 4 == 0 && ((uintptr_t)X & 15) == 0; }
 
 }  // namespace
 
 extern "C" {
 
 int n2v_knn_inv_norms(const float *X, int64_t n, int32_t dim, float *inv_norm, void *stream) {
-  if (dim < 1 || dim > 1024 || n < 0 || n >= ((int64_t)1 << 31)) return N2V_EINVAL;
+  if (!matrix_ok(n, dim)) return N2V_EINVAL;
   if (n == 0) return N2V_OK;
   if (!X || !inv_norm) return N2V_EINVAL;
   const int64_t blocks = (n + 3) / 4 < 65536 ? (n + 3) / 4 : 65536;
@@ -326,11 +332,12 @@ int n2v_knn_inv_norms(const float *X, int64_t n, int32_t dim, float *inv_norm, v
 }
 
 int64_t n2v_knn_workspace_bytes(int64_t n, int32_t dim, int64_t n_queries, int32_t k) {
-  if (dim < 1 || dim > 1024 || n < 0 || n >= ((int64_t)1 << 31) || n_queries < 0 || k < 0 || k > kMaxK) return -1;
+  if (!matrix_ok(n, dim) || n_queries < 0 || k < 0 || k > kMaxK) return -1;
   if (n == 0 || n_queries == 0) return 0;
-  if (k == 0) return qhat_only_bytes(dim, n_queries);
-  const TopkPlan p = plan_topk(n, dim, n_queries, k);
-  return p.qhat_bytes + 4 * p.part_bytes;
+  if (k > 0) return plan_topk(n, dim, n_queries, k, nullptr).bytes;
+  Carver carve(nullptr);  // n2v_knn_scores: q_hat alone
+  take_qhat(carve, dim, n_queries);
+  return carve.used;
 }
 
 int n2v_knn_topk(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *queries,
@@ -339,28 +346,20 @@ int n2v_knn_topk(const float *X, const float *inv_norm, int64_t n, int32_t dim, 
   if (!args_ok(X, inv_norm, n, dim, queries, query_rows, n_queries)) return N2V_EINVAL;
   if (k < 1 || k > kMaxK) return N2V_EINVAL;
   if (n == 0 || n_queries == 0) return N2V_OK;
-  if (!out_rows || !out_scores || !workspace || ((uintptr_t)workspace & 15)) return N2V_EINVAL;
-  if (workspace_bytes < n2v_knn_workspace_bytes(n, dim, n_queries, k)) return N2V_EINVAL;
-  const TopkPlan p = plan_topk(n, dim, n_queries, k);
+  const TopkPlan p = plan_topk(n, dim, n_queries, k, workspace);
+  if (!out_rows || !out_scores || !workspace_ok(workspace, workspace_bytes, p.bytes)) return N2V_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  char *ws = (char *)workspace;
-  float *qhat = (float *)ws;
-  float *s0 = (float *)(ws + p.qhat_bytes);
-  int32_t *r0 = (int32_t *)(ws + p.qhat_bytes + p.part_bytes);
-  float *s1 = (float *)(ws + p.qhat_bytes + 2 * p.part_bytes);
-  int32_t *r1 = (int32_t *)(ws + p.qhat_bytes + 3 * p.part_bytes);
-  int rc = launch_queries(X, inv_norm, dim, queries, query_rows, n_queries, p.nq_pad, qhat, st);
+  const int rc = launch_queries(X, inv_norm, dim, queries, query_rows, n_queries, p.qhat, st);
   if (rc != N2V_OK) return rc;
-  const bool vec = vec_ok(X, dim);
   switch (p.variant) {
-    case 0: rc = launch_topk<4, 64, 256>(vec, p, X, inv_norm, n, dim, qhat, n_queries, k, s0, r0, st); break;
-    case 1: rc = launch_topk<2, 32, 512>(vec, p, X, inv_norm, n, dim, qhat, n_queries, k, s0, r0, st); break;
-    case 2: rc = launch_topk<1, 16, 1024>(vec, p, X, inv_norm, n, dim, qhat, n_queries, k, s0, r0, st); break;
-    default: rc = launch_topk<1, 8, 2048>(vec, p, X, inv_norm, n, dim, qhat, n_queries, k, s0, r0, st); break;
+    case 0: launch_topk<4, 64, 256>(p, X, inv_norm, n, dim, n_queries, k, st); break;
+    case 1: launch_topk<2, 32, 512>(p, X, inv_norm, n, dim, n_queries, k, st); break;
+    case 2: launch_topk<1, 16, 1024>(p, X, inv_norm, n, dim, n_queries, k, st); break;
+    default: launch_topk<1, 8, 2048>(p, X, inv_norm, n, dim, n_queries, k, st); break;
   }
-  if (rc != N2V_OK) return rc;
-  hipLaunchKernelGGL(merge_kernel, dim3((unsigned)n_queries), dim3(256), 0, st, s0, r0, s1, r1, p.n_chunks, k,
-                     out_rows, out_scores);
+  N2V_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(merge_kernel, dim3((unsigned)n_queries), dim3(256), 0, st, p.s0, p.r0, p.s1, p.r1, p.n_chunks,
+                     k, out_rows, out_scores);
   N2V_HIP_CHECK(hipGetLastError());
   return N2V_OK;
 }
@@ -370,18 +369,17 @@ int n2v_knn_scores(const float *X, const float *inv_norm, int64_t n, int32_t dim
                    int64_t workspace_bytes, void *stream) {
   if (!args_ok(X, inv_norm, n, dim, queries, query_rows, n_queries)) return N2V_EINVAL;
   if (n == 0 || n_queries == 0) return N2V_OK;
-  if (!out_scores || !workspace || ((uintptr_t)workspace & 15)) return N2V_EINVAL;
-  if (workspace_bytes < n2v_knn_workspace_bytes(n, dim, n_queries, 0)) return N2V_EINVAL;
+  Carver carve(workspace);
+  float *qhat = take_qhat(carve, dim, n_queries);
+  if (!out_scores || !workspace_ok(workspace, workspace_bytes, carve.used)) return N2V_EINVAL;
   if ((n_queries + 15) / 16 > 65535) return N2V_EINVAL;  // grid y; callers split larger batches
   hipStream_t st = (hipStream_t)stream;
-  float *qhat = (float *)workspace;
-  int rc = launch_queries(X, inv_norm, dim, queries, query_rows, n_queries, nq_pad_of(n_queries), qhat, st);
+  const int rc = launch_queries(X, inv_norm, dim, queries, query_rows, n_queries, qhat, st);
   if (rc != N2V_OK) return rc;
   const dim3 grid((unsigned)((n + 63) / 64), (unsigned)((n_queries + 15) / 16));
-  if (vec_ok(X, dim))
-    hipLaunchKernelGGL(scores_kernel<true>, grid, dim3(256), 0, st, X, inv_norm, n, dim, qhat, n_queries, out_scores);
-  else
-    hipLaunchKernelGGL(scores_kernel<false>, grid, dim3(256), 0, st, X, inv_norm, n, dim, qhat, n_queries, out_scores);
+  with_bool(vec_ok(dim, X), [&](auto VEC) {
+    hipLaunchKernelGGL(scores_kernel<VEC>, grid, dim3(256), 0, st, X, inv_norm, n, dim, qhat, n_queries, out_scores);
+  });
   N2V_HIP_CHECK(hipGetLastError());
   return N2V_OK;
 }

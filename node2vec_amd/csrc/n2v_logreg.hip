@@ -20,30 +20,30 @@
 
 namespace {
 
-constexpr int kStepRows = 64;                  // rows per block step: 16 per wave, 4 waves
-constexpr int kMaxSlabs = 2048;                // blocks of the launch (8 per CU)
-constexpr int64_t kPartialsCap = 512ll << 20;  // bytes of slab partials at most
+constexpr int kStepRows = kSlabStepRows;
 constexpr int kMaxClasses = 1024;
 
+// the slabs, and the workspace `ws` laid out (ws null: only `bytes` means anything): W padded to [c_pad][dim_pad],
+// the slabs' partial GW, Gb and L, and the folded Lk
 struct Plan {
-  int64_t slab_rows, c_pad, wpad_bytes, gw_bytes, gb_bytes, l_bytes, lk_bytes;
-  int32_t n_slabs;
+  SlabPlan slabs;
+  int64_t c_pad, bytes;
+  float *wpad, *GW, *Gb;
+  double *L, *Lk;
 };
 
-Plan plan_of(int64_t n, int32_t dim, int32_t c) {
+Plan plan_of(int64_t n, int32_t dim, int32_t c, void *ws) {
   Plan p{};
-  const int64_t per_slab = 4 * (int64_t)c * (dim + 3);  // GW and Gb in fp32, L in fp64
-  int64_t most = kPartialsCap / per_slab;                // >= 127: per_slab <= 4 MiB + 12 KiB
-  if (most > kMaxSlabs) most = kMaxSlabs;
-  const int64_t share = (n + most - 1) / most;
-  p.slab_rows = round_up(share < 1 ? 1 : share, kStepRows);
-  p.n_slabs = (int32_t)((n + p.slab_rows - 1) / p.slab_rows);
+  p.slabs = slab_plan(n, 4 * (int64_t)c * (dim + 3));  // GW and Gb in fp32, L in fp64
   p.c_pad = round_up(c, 64);
-  p.wpad_bytes = round_up(p.c_pad * dim_pad_of(dim) * 4, 256);
-  p.gw_bytes = round_up((int64_t)p.n_slabs * c * dim * 4, 256);
-  p.gb_bytes = round_up((int64_t)p.n_slabs * c * 4, 256);
-  p.l_bytes = round_up((int64_t)p.n_slabs * c * 8, 256);
-  p.lk_bytes = round_up((int64_t)c * 8, 256);
+  const int64_t sc = (int64_t)p.slabs.n_slabs * c;
+  Carver carve(ws);
+  p.wpad = carve.take<float>(p.c_pad * dim_pad_of(dim) * 4);
+  p.GW = carve.take<float>(sc * dim * 4);
+  p.Gb = carve.take<float>(sc * 4);
+  p.L = carve.take<double>(sc * 8);
+  p.Lk = carve.take<double>((int64_t)c * 8);
+  p.bytes = carve.used;
   return p;
 }
 
@@ -85,18 +85,6 @@ __device__ inline float log1p01(float e) {
   g = __fmaf_rn(g, e, -0x1.0p-1f);
   const float u = e * g;
   return __fmaf_rn(e, u, e);
-}
-
-// W padded to [c_pad][dim_pad] with zeros; one wave per padded row
-__global__ __launch_bounds__(256) void prep_kernel(const float *__restrict__ W, int32_t c, int64_t c_pad, int32_t dim,
-                                                   float *__restrict__ wpad) {
-  const int lane = threadIdx.x & 63;
-  const int32_t dp = dim_pad_of(dim);
-  const int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (k >= c_pad) return;
-  const bool live = k < c;
-  const float *v = W + (live ? k : 0) * dim;
-  for (int d = lane; d < dp; d += 64) wpad[k * dp + d] = (live && d < dim) ? v[d] : 0.f;
 }
 
 // a wave scores 16 rows per step against every class; the steps of 64 rows go round the grid
@@ -276,37 +264,7 @@ __global__ void loss_kernel(const double *__restrict__ Lk, int32_t c, double *__
   loss[0] = s;
 }
 
-bool sizes_ok(int64_t n, int32_t dim, int32_t c) {
-  return dim >= 1 && dim <= 1024 && n >= 0 && n < ((int64_t)1 << 31) && c >= 1 && c <= kMaxClasses;
-}
-
-bool workspace_ok(const void *ws, int64_t ws_bytes, int64_t n, int32_t dim, int32_t c) {
-  return ws && ((uintptr_t)ws & 15) == 0 && ws_bytes >= n2v_logreg_workspace_bytes(n, dim, c);
-}
-
-void launch_prep(const Plan &p, hipStream_t st, const float *W, int32_t c, int32_t dim, float *wpad) {
-  hipLaunchKernelGGL(prep_kernel, dim3((unsigned)((p.c_pad + 3) / 4)), dim3(256), 0, st, W, c, p.c_pad, dim, wpad);
-}
-
-template <int G>
-void launch_scores(bool vec, unsigned blocks, hipStream_t st, const float *X, int64_t n, int32_t dim,
-                   const float *wpad, const float *b, int32_t c, float *Z) {
-  if (vec)
-    hipLaunchKernelGGL((scores_kernel<G, true>), dim3(blocks), dim3(256), 0, st, X, n, dim, wpad, b, c, Z);
-  else
-    hipLaunchKernelGGL((scores_kernel<G, false>), dim3(blocks), dim3(256), 0, st, X, n, dim, wpad, b, c, Z);
-}
-
-template <int G>
-void launch_loss_grad(bool vec, const Plan &p, hipStream_t st, const float *X, const uint32_t *y_bits, int64_t n,
-                      int32_t dim, const float *wpad, const float *b, int32_t c, float *GW, float *Gb, double *L) {
-  if (vec)
-    hipLaunchKernelGGL((loss_grad_kernel<G, true>), dim3((unsigned)p.n_slabs), dim3(256), 0, st, X, y_bits, n, dim,
-                       wpad, b, c, GW, Gb, L, p.slab_rows);
-  else
-    hipLaunchKernelGGL((loss_grad_kernel<G, false>), dim3((unsigned)p.n_slabs), dim3(256), 0, st, X, y_bits, n, dim,
-                       wpad, b, c, GW, Gb, L, p.slab_rows);
-}
+bool sizes_ok(int64_t n, int32_t dim, int32_t c) { return matrix_ok(n, dim) && c >= 1 && c <= kMaxClasses; }
 
 }  // namespace
 
@@ -314,33 +272,28 @@ extern "C" {
 
 int64_t n2v_logreg_slab_rows(int64_t n, int32_t dim, int32_t c) {
   if (!sizes_ok(n, dim, c)) return -1;
-  return plan_of(n, dim, c).slab_rows;
+  return plan_of(n, dim, c, nullptr).slabs.slab_rows;
 }
 
 int64_t n2v_logreg_workspace_bytes(int64_t n, int32_t dim, int32_t c) {
   if (!sizes_ok(n, dim, c)) return -1;
-  if (n == 0) return 0;
-  const Plan p = plan_of(n, dim, c);
-  return p.wpad_bytes + p.gw_bytes + p.gb_bytes + p.l_bytes + p.lk_bytes;
+  return n == 0 ? 0 : plan_of(n, dim, c, nullptr).bytes;
 }
 
 int n2v_logreg_scores(const float *X, int64_t n, int32_t dim, const float *W, const float *b, int32_t c,
                       float *scores_out, void *workspace, int64_t workspace_bytes, void *stream) {
   if (!sizes_ok(n, dim, c)) return N2V_EINVAL;
   if (n == 0) return N2V_OK;
-  if (!X || !W || !b || !scores_out || !workspace_ok(workspace, workspace_bytes, n, dim, c)) return N2V_EINVAL;
-  const Plan p = plan_of(n, dim, c);
+  const Plan p = plan_of(n, dim, c, workspace);
+  if (!X || !W || !b || !scores_out || !workspace_ok(workspace, workspace_bytes, p.bytes)) return N2V_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  float *wpad = (float *)workspace;
-  launch_prep(p, st, W, c, dim, wpad);
+  launch_pad_rows(st, W, c, p.c_pad, dim, p.wpad, nullptr);
   N2V_HIP_CHECK(hipGetLastError());
   const int64_t steps = (n + kStepRows - 1) / kStepRows;
   const unsigned blocks = (unsigned)(steps < 4096 ? steps : 4096);
-  const bool vec = dim % 4 == 0 && ((uintptr_t)X & 15) == 0;
-  if (c <= 16)  // one group of 16 classes per tile; the bits do not depend on the tile
-    launch_scores<1>(vec, blocks, st, X, n, dim, wpad, b, c, scores_out);
-  else
-    launch_scores<4>(vec, blocks, st, X, n, dim, wpad, b, c, scores_out);
+  with_tile(c, vec_ok(dim, X), [&](auto G, auto VEC) {
+    hipLaunchKernelGGL((scores_kernel<G, VEC>), dim3(blocks), dim3(256), 0, st, X, n, dim, p.wpad, b, c, scores_out);
+  });
   N2V_HIP_CHECK(hipGetLastError());
   return N2V_OK;
 }
@@ -350,30 +303,23 @@ int n2v_logreg_loss_grad(const float *X, const uint32_t *y_bits, int64_t n, int3
                          void *workspace, int64_t workspace_bytes, void *stream) {
   if (!sizes_ok(n, dim, c)) return N2V_EINVAL;
   if (n == 0) return N2V_OK;
+  const Plan p = plan_of(n, dim, c, workspace);
   if (!X || !y_bits || !W || !b || !loss_out || !grad_w_out || !grad_b_out ||
-      !workspace_ok(workspace, workspace_bytes, n, dim, c))
+      !workspace_ok(workspace, workspace_bytes, p.bytes))
     return N2V_EINVAL;
-  const Plan p = plan_of(n, dim, c);
   hipStream_t st = (hipStream_t)stream;
-  char *ws = (char *)workspace;
-  float *wpad = (float *)ws;
-  float *GW = (float *)(ws + p.wpad_bytes);
-  float *Gb = (float *)(ws + p.wpad_bytes + p.gw_bytes);
-  double *L = (double *)(ws + p.wpad_bytes + p.gw_bytes + p.gb_bytes);
-  double *Lk = (double *)(ws + p.wpad_bytes + p.gw_bytes + p.gb_bytes + p.l_bytes);
-  launch_prep(p, st, W, c, dim, wpad);
+  launch_pad_rows(st, W, c, p.c_pad, dim, p.wpad, nullptr);
   N2V_HIP_CHECK(hipGetLastError());
-  const bool vec = dim % 4 == 0 && ((uintptr_t)X & 15) == 0;
-  if (c <= 16)
-    launch_loss_grad<1>(vec, p, st, X, y_bits, n, dim, wpad, b, c, GW, Gb, L);
-  else
-    launch_loss_grad<4>(vec, p, st, X, y_bits, n, dim, wpad, b, c, GW, Gb, L);
+  with_tile(c, vec_ok(dim, X), [&](auto G, auto VEC) {
+    hipLaunchKernelGGL((loss_grad_kernel<G, VEC>), dim3((unsigned)p.slabs.n_slabs), dim3(256), 0, st, X, y_bits, n,
+                       dim, p.wpad, b, c, p.GW, p.Gb, p.L, p.slabs.slab_rows);
+  });
   N2V_HIP_CHECK(hipGetLastError());
   const int64_t elems = (int64_t)c * dim + c;
-  hipLaunchKernelGGL(fold_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, GW, Gb, L, p.n_slabs, c,
-                     dim, grad_w_out, grad_b_out, Lk);
+  hipLaunchKernelGGL(fold_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, p.GW, p.Gb, p.L,
+                     p.slabs.n_slabs, c, dim, grad_w_out, grad_b_out, p.Lk);
   N2V_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(1), 0, st, Lk, c, loss_out);
+  hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(1), 0, st, p.Lk, c, loss_out);
   N2V_HIP_CHECK(hipGetLastError());
   return N2V_OK;
 }

@@ -23,7 +23,7 @@
 // pointer that is not 16-byte aligned goes element by element through the same guards (VEC = false).
 #include <math.h>
 
-#include "n2v_common.h"
+#include "n2v_dense_host.h"
 
 namespace {
 
@@ -204,8 +204,19 @@ __global__ __launch_bounds__(256) void pairs_in_graph_kernel(const int64_t *__re
   out_mask[i] = hit;
 }
 
-// lane group and chunks per lane of a dimension (the file header's G; K = ceil(dim / 4 G))
-inline int group_of(int32_t dim) { return dim <= 128 ? 16 : dim <= 256 ? 32 : 64; }
+// f(G, K, VEC) as template arguments: the lane group of a dimension (the file header's G), K = ceil(dim / 4 G)
+// chunks per lane, and the load path
+template <typename F>
+void with_shape(int32_t dim, bool vec, F &&f) {
+  with_bool(vec, [&](auto v) {
+    if (dim <= 64) f(std::integral_constant<int, 16>{}, std::integral_constant<int, 1>{}, v);
+    else if (dim <= 128) f(std::integral_constant<int, 16>{}, std::integral_constant<int, 2>{}, v);
+    else if (dim <= 256) f(std::integral_constant<int, 32>{}, std::integral_constant<int, 2>{}, v);
+    else if (dim <= 512) f(std::integral_constant<int, 64>{}, std::integral_constant<int, 2>{}, v);
+    else if (dim <= 768) f(std::integral_constant<int, 64>{}, std::integral_constant<int, 3>{}, v);
+    else f(std::integral_constant<int, 64>{}, std::integral_constant<int, 4>{}, v);
+  });
+}
 
 bool grid_of(int64_t n_pairs, unsigned &blocks) {
   const int64_t g = (n_pairs + kBlockPairs - 1) / kBlockPairs;
@@ -214,31 +225,7 @@ bool grid_of(int64_t n_pairs, unsigned &blocks) {
   return true;
 }
 
-template <int G, int K>
-void launch_scores(bool vec, unsigned blocks, hipStream_t st, const float *X, const float *inv_norm, int64_t n,
-                   int32_t dim, const int64_t *a, const int64_t *b, int64_t n_pairs, float *out) {
-  if (vec)
-    hipLaunchKernelGGL((pair_scores_kernel<G, K, true>), dim3(blocks), dim3(256), 0, st, X, inv_norm, n, dim, a, b,
-                       n_pairs, out);
-  else
-    hipLaunchKernelGGL((pair_scores_kernel<G, K, false>), dim3(blocks), dim3(256), 0, st, X, inv_norm, n, dim, a, b,
-                       n_pairs, out);
-}
-
-template <int G, int K>
-void launch_features(bool vec, unsigned blocks, hipStream_t st, const float *X, int64_t n, int32_t dim,
-                     const int64_t *a, const int64_t *b, int64_t n_pairs, int32_t op, float *out) {
-  if (vec)
-    hipLaunchKernelGGL((pair_features_kernel<G, K, true>), dim3(blocks), dim3(256), 0, st, X, n, dim, a, b, n_pairs,
-                       op, out);
-  else
-    hipLaunchKernelGGL((pair_features_kernel<G, K, false>), dim3(blocks), dim3(256), 0, st, X, n, dim, a, b,
-                       n_pairs, op, out);
-}
-
-bool sizes_ok(int64_t n, int32_t dim, int64_t n_pairs) {
-  return dim >= 1 && dim <= 1024 && n >= 0 && n < ((int64_t)1 << 31) && n_pairs >= 0;
-}
+bool sizes_ok(int64_t n, int32_t dim, int64_t n_pairs) { return matrix_ok(n, dim) && n_pairs >= 0; }
 
 }  // namespace
 
@@ -254,15 +241,10 @@ int n2v_pair_scores(const float *X, const float *inv_norm, int64_t n, int32_t di
   if (n_pairs == 0) return N2V_OK;
   if (!X || !a || !b || !out_scores) return N2V_EINVAL;
   if (metric == N2V_PAIR_DOT) inv_norm = nullptr;  // ignored
-  hipStream_t st = (hipStream_t)stream;
-  const bool vec = dim % 4 == 0 && ((uintptr_t)X & 15) == 0;
-  const int G = group_of(dim), K = (dim + 4 * G - 1) / (4 * G);
-  if (G == 16 && K == 1) launch_scores<16, 1>(vec, blocks, st, X, inv_norm, n, dim, a, b, n_pairs, out_scores);
-  else if (G == 16) launch_scores<16, 2>(vec, blocks, st, X, inv_norm, n, dim, a, b, n_pairs, out_scores);
-  else if (G == 32) launch_scores<32, 2>(vec, blocks, st, X, inv_norm, n, dim, a, b, n_pairs, out_scores);
-  else if (K == 2) launch_scores<64, 2>(vec, blocks, st, X, inv_norm, n, dim, a, b, n_pairs, out_scores);
-  else if (K == 3) launch_scores<64, 3>(vec, blocks, st, X, inv_norm, n, dim, a, b, n_pairs, out_scores);
-  else launch_scores<64, 4>(vec, blocks, st, X, inv_norm, n, dim, a, b, n_pairs, out_scores);
+  with_shape(dim, vec_ok(dim, X), [&](auto G, auto K, auto VEC) {
+    hipLaunchKernelGGL((pair_scores_kernel<G, K, VEC>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, X, inv_norm,
+                       n, dim, a, b, n_pairs, out_scores);
+  });
   N2V_HIP_CHECK(hipGetLastError());
   return N2V_OK;
 }
@@ -275,15 +257,10 @@ int n2v_pair_features(const float *X, int64_t n, int32_t dim, const int64_t *a, 
   if (!grid_of(n_pairs, blocks)) return N2V_EINVAL;
   if (n_pairs == 0) return N2V_OK;
   if (!X || !a || !b || !out) return N2V_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const bool vec = dim % 4 == 0 && (((uintptr_t)X | (uintptr_t)out) & 15) == 0;
-  const int G = group_of(dim), K = (dim + 4 * G - 1) / (4 * G);
-  if (G == 16 && K == 1) launch_features<16, 1>(vec, blocks, st, X, n, dim, a, b, n_pairs, op, out);
-  else if (G == 16) launch_features<16, 2>(vec, blocks, st, X, n, dim, a, b, n_pairs, op, out);
-  else if (G == 32) launch_features<32, 2>(vec, blocks, st, X, n, dim, a, b, n_pairs, op, out);
-  else if (K == 2) launch_features<64, 2>(vec, blocks, st, X, n, dim, a, b, n_pairs, op, out);
-  else if (K == 3) launch_features<64, 3>(vec, blocks, st, X, n, dim, a, b, n_pairs, op, out);
-  else launch_features<64, 4>(vec, blocks, st, X, n, dim, a, b, n_pairs, op, out);
+  with_shape(dim, vec_ok(dim, X, out), [&](auto G, auto K, auto VEC) {
+    hipLaunchKernelGGL((pair_features_kernel<G, K, VEC>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, X, n, dim,
+                       a, b, n_pairs, op, out);
+  });
   N2V_HIP_CHECK(hipGetLastError());
   return N2V_OK;
 }

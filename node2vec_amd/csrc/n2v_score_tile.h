@@ -1,15 +1,14 @@
-// n2v_score_tile.h -- the fixed-order fp32 pieces n2v_knn.hip and n2v_kmeans.hip share: the sum of
-// squares of a row (wave_sumsq), 1 / sqrt or 0, and the 16 x 16 MFMA dot chain (score_tile).  Every
-// caller gets the same bits from the same code (DESIGN.md "Nearest neighbours", "Clustering").
+// n2v_score_tile.h -- the fixed-order fp32 pieces n2v_knn.hip, n2v_kmeans.hip and n2v_logreg.hip share: the sum of
+// squares of a row (wave_sumsq), 1 / sqrt or 0, the 16 x 16 MFMA dot chain (score_tile) and the kernel that pads
+// its operand B (pad_rows_kernel).  Every caller gets the same bits from the same code (DESIGN.md "Nearest
+// neighbours", "Clustering", "Node classification"); what surrounds the kernels on the host is n2v_dense_host.h.
 #pragma once
 
-#include "n2v_common.h"
+#include "n2v_dense_host.h"
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__host__ __device__ inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 
 // rows of the padded operand matrix [rows_pad][dim_pad] are dim_pad floats long (zeros in the padding)
 __host__ __device__ inline int32_t dim_pad_of(int32_t dim) { return (int32_t)round_up(dim, 16); }
@@ -24,6 +23,32 @@ __device__ inline float wave_sumsq(const float *__restrict__ v, int32_t dim, int
 }
 
 __device__ inline float inv_sqrt_or_zero(float s) { return s > 0.f ? 1.f / sqrtf(s) : 0.f; }
+
+// The rows of src[n_rows][dim] padded with zeros to dst[rows_pad][dim_pad], score_tile's operand B, and with
+// `sumsq` (may be null) wave_sumsq of every row, 0 for a padding row; one wave per padded row.  (Kernel and
+// launcher are templates so that only the files that launch it carry the kernel.)
+template <typename = void>
+__global__ __launch_bounds__(256) void pad_rows_kernel(const float *__restrict__ src, int32_t n_rows,
+                                                       int64_t rows_pad, int32_t dim, float *__restrict__ dst,
+                                                       float *__restrict__ sumsq) {
+  const int lane = threadIdx.x & 63;
+  const int32_t dp = dim_pad_of(dim);
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows_pad) return;
+  const bool live = r < n_rows;
+  const float *v = src + (live ? r : 0) * dim;
+  for (int d = lane; d < dp; d += 64) dst[r * dp + d] = (live && d < dim) ? v[d] : 0.f;
+  if (!sumsq) return;
+  const float s = wave_sumsq(v, dim, lane);
+  if (lane == 0) sumsq[r] = live ? s : 0.f;
+}
+
+template <typename T = void>
+void launch_pad_rows(hipStream_t st, const float *src, int32_t n_rows, int64_t rows_pad, int32_t dim,
+                            float *dst, float *sumsq) {
+  hipLaunchKernelGGL(pad_rows_kernel<T>, dim3((unsigned)((rows_pad + 3) / 4)), dim3(256), 0, st, src, n_rows, rows_pad,
+                     dim, dst, sumsq);
+}
 
 // Dot products of 16 rows (row0 ..) with G groups of 16 queries, one wave: acc[g][i] is
 // dot(q_hat[16 g + (lane & 15)], x[row0 + 4 (lane >> 4) + i]).  The X tile is operand A (lane l:

@@ -339,13 +339,13 @@ class KeyedVectors:
         first rows are clustered."""
         from node2vec_amd import cluster
 
-        cluster._check_metric(metric)
+        cluster.check_metric(metric)
         n = len(self)
         if restrict_vocab is not None:
             if int(restrict_vocab) < 0:
                 raise ValueError("restrict_vocab must be >= 0")
             n = min(n, int(restrict_vocab))
-        cluster._check_k(k, n)
+        cluster.check_k(k, n)
         X = self._device_vectors()[:n]
         inv_norm = None
         if metric == "cosine":

@@ -14,7 +14,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from node2vec_amd import _lib, similarity
+from node2vec_amd import _dense, _lib, similarity
 
 METRICS = {"dot": _lib.PAIR_DOT, "cosine": _lib.PAIR_COSINE}
 OPERATORS = {"average": _lib.PAIR_AVERAGE, "hadamard": _lib.PAIR_HADAMARD, "l1": _lib.PAIR_L1, "l2": _lib.PAIR_L2}
@@ -41,7 +41,7 @@ def pair_scores(X: torch.Tensor, a, b, metric: str = "cosine", inv_norm: Optiona
     cosine; a row holding NaN or inf scores NaN."""
     if metric not in METRICS:
         raise ValueError(f"metric {metric!r}: " + " | ".join(METRICS))
-    X = similarity._matrix(X)
+    X = _dense.matrix(X)
     n = X.shape[0]
     a, b = _pairs(a, b, n, X.device)
     out = torch.empty(a.shape[0], dtype=torch.float32, device=X.device)
@@ -65,7 +65,7 @@ def pair_features(X: torch.Tensor, a, b, op: str = "hadamard", out: Optional[tor
     fp32 [n_pairs, dim] tensor on X's device to fill (and return)."""
     if op not in OPERATORS:
         raise ValueError(f"operator {op!r}: " + " | ".join(OPERATORS))
-    X = similarity._matrix(X)
+    X = _dense.matrix(X)
     n, dim = X.shape
     a, b = _pairs(a, b, n, X.device)
     if a.shape[0] * dim >= 1 << 31:

@@ -13,28 +13,16 @@ from typing import Optional, Tuple
 
 import torch
 
-from node2vec_amd import _lib
+from node2vec_amd import _dense, _lib
 
-MAX_DIM = 1024
+MAX_DIM = _dense.MAX_DIM
 MAX_FUSED_K = 1024  # n2v_knn_topk's limit; larger k go through the full scores and a stable sort
 WORKSPACE_LIMIT = 1 << 30  # bytes of workspace (or of full scores) per launch: query batches are split to fit
 
 
-def _matrix(X: torch.Tensor) -> torch.Tensor:
-    if not isinstance(X, torch.Tensor) or X.ndim != 2 or not X.is_cuda:
-        raise ValueError("X must be a 2-D tensor on a HIP device")
-    if X.dtype != torch.float32:
-        raise ValueError(f"X must be float32, not {X.dtype}")
-    if not 1 <= X.shape[1] <= MAX_DIM:
-        raise ValueError(f"vector dimension {X.shape[1]} outside [1, {MAX_DIM}]")
-    if X.shape[0] >= 1 << 31:
-        raise ValueError("at most 2^31 - 1 rows")
-    return X.contiguous()
-
-
 def inv_norms(X: torch.Tensor) -> torch.Tensor:
     """1 / ||x_r|| for every row (0 for a zero row), fp32 [n]: the norms init_sims computes."""
-    X = _matrix(X)
+    X = _dense.matrix(X)
     out = torch.empty(X.shape[0], dtype=torch.float32, device=X.device)
     with torch.cuda.device(X.device):
         _lib.check(_lib.load().n2v_knn_inv_norms(X.data_ptr(), X.shape[0], X.shape[1], out.data_ptr(),
@@ -44,7 +32,7 @@ def inv_norms(X: torch.Tensor) -> torch.Tensor:
 
 def _inputs(X, queries, rows, restrict, inv_norm):
     """(X', inv_norm', queries, rows): X' the rows [0, restrict); a query row outside them becomes its vector"""
-    X = _matrix(X)
+    X = _dense.matrix(X)
     if (queries is None) == (rows is None):
         raise ValueError("give exactly one of queries= / rows=")
     n = X.shape[0]
@@ -76,10 +64,6 @@ def _inputs(X, queries, rows, restrict, inv_norm):
     return X, inv_norm, queries, rows
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def _scores(X, inv_norm, queries, rows) -> torch.Tensor:
     L = _lib.load()
     n, dim = X.shape
@@ -87,8 +71,8 @@ def _scores(X, inv_norm, queries, rows) -> torch.Tensor:
     out = torch.empty((nq, n), dtype=torch.float32, device=X.device)
     if n == 0 or nq == 0:
         return out
-    ws = torch.empty(max(int(L.n2v_knn_workspace_bytes(n, dim, nq, 0)), 16), dtype=torch.uint8, device=X.device)
-    _lib.check(L.n2v_knn_scores(X.data_ptr(), inv_norm.data_ptr(), n, dim, _ptr(queries), _ptr(rows), nq,
+    ws = _dense.workspace(L.n2v_knn_workspace_bytes, n, dim, nq, 0, device=X.device)
+    _lib.check(L.n2v_knn_scores(X.data_ptr(), inv_norm.data_ptr(), n, dim, _dense.ptr(queries), _dense.ptr(rows), nq,
                                 out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
                "n2v_knn_scores")
     return out
@@ -120,11 +104,10 @@ def _topk_fused(X, inv_norm, queries, rows, k):
         step = (step + 1) // 2
     for i in range(0, nq, step):
         j = min(nq, i + step)
-        ws = torch.empty(max(int(L.n2v_knn_workspace_bytes(n, dim, j - i, k)), 16), dtype=torch.uint8,
-                         device=X.device)
+        ws = _dense.workspace(L.n2v_knn_workspace_bytes, n, dim, j - i, k, device=X.device)
         q = None if queries is None else queries[i:j]
         r = None if rows is None else rows[i:j]
-        _lib.check(L.n2v_knn_topk(X.data_ptr(), inv_norm.data_ptr(), n, dim, _ptr(q), _ptr(r), j - i, k,
+        _lib.check(L.n2v_knn_topk(X.data_ptr(), inv_norm.data_ptr(), n, dim, _dense.ptr(q), _dense.ptr(r), j - i, k,
                                   out_r[i:j].data_ptr(), out_s[i:j].data_ptr(), ws.data_ptr(), ws.numel(),
                                   _lib.current_stream_ptr()), "n2v_knn_topk")
     return out_r, out_s

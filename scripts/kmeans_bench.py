@@ -90,7 +90,7 @@ def main():
             dist = torch.empty(n, dtype=torch.float32, device=dev)
             nxt, counts = torch.empty_like(C), torch.zeros(k, dtype=torch.int64, device=dev)
             stats = torch.zeros(2, dtype=torch.int64, device=dev)
-            ws = cluster._workspace(n, dim, k, dev)
+            ws = cluster.alloc_workspace(n, dim, k, dev)
 
             def step():
                 _lib.check(L.n2v_kmeans_step(X.data_ptr(), None, n, dim, C.data_ptr(), k, _lib.KMEANS_EUCLIDEAN,

@@ -71,7 +71,7 @@ def main():
             Y = Yb.float()  # the baseline's labels, made outside the timed region
             del Yb
             out = torch.zeros(1 + c * dim + c, dtype=torch.float64, device=dev)
-            ws = classify._workspace(n, dim, c, dev)
+            ws = classify.alloc_workspace(n, dim, c, dev)
 
             def call():
                 _lib.check(L.n2v_logreg_loss_grad(X.data_ptr(), y_bits.data_ptr(), n, dim, W.data_ptr(), b.data_ptr(),

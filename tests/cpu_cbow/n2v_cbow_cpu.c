@@ -2,9 +2,8 @@
  * n2v_cbow_cpu.c -- single-thread CPU restatement of CBOW with negative sampling.
  *
  * TEST INFRASTRUCTURE ONLY: tests/test_cbow_*.py build it once per session with
- * cc -O2 -fPIC -shared -ffp-contract=off -fno-fast-math -std=c11 (the flags of
- * tests/cpu_hs/n2v_hs_cpu.c) and pin node2vec_amd/csrc/n2v_cbow.hip to it bit for bit in
- * deterministic mode.
+ * the flags of tests/cpu_build.py (no contraction, no fast-math) and pin
+ * node2vec_amd/csrc/n2v_cbow.hip to it bit for bit in deterministic mode.
  *
  * The algorithm is gensim 3.8 train_batch_cbow / fast_sentence_cbow_neg (gensim cannot run here;
  * this file is the pin).  Sentence preparation is that of the skip-gram kernel: tokens < 0 or

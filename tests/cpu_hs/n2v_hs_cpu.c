@@ -1,8 +1,8 @@
 /*
  * n2v_hs_cpu.c -- single-thread CPU restatement of skip-gram hierarchical softmax.
  *
- * TEST INFRASTRUCTURE ONLY: tests/test_hs_*.py build it once per session with
- * cc -O2 -fPIC -shared -ffp-contract=off -fno-fast-math -std=c11 (the oracle's flags) and pin
+ * TEST INFRASTRUCTURE ONLY: tests/test_hs_*.py build it once per session with the flags of
+ * tests/cpu_build.py (no contraction, no fast-math: the oracle's flags) and pin
  * node2vec_amd/csrc/n2v_hs.hip to it bit for bit in deterministic mode.
  *
  * The algorithm is word2vec.c / Spark MLlib Word2Vec skip-gram with hierarchical softmax, as

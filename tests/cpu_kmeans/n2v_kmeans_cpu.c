@@ -1,5 +1,5 @@
 /* CPU restatement of node2vec_amd/csrc/n2v_kmeans.hip: assignment, update and the fused step in the kernels'
- * fixed orders.  Built by tests/kmeans_cases.py with -ffp-contract=off, so every line below is the fp32 or
+ * fixed orders.  Built with the flags of tests/cpu_build.py (no contraction), so every line below is the fp32 or
  * fp64 operation it spells.  This text is the contract; the kernels are held to its bits.
  *
  * dot(c, x):  acc = +0; for d0 = 0, 16, .. < round_up(dim, 16), j = 0..3, k = 0..3, d = d0 + 4 k + j:

@@ -1,6 +1,6 @@
 /* CPU restatement of node2vec_amd/csrc/n2v_logreg.hip: the scores, the spelled exp / log1p, the slab chains of the
- * fused loss-and-gradient pass and the fp64 fold.  Built by tests/logreg_cases.py with -ffp-contract=off, so every
- * line below is the fp32 or fp64 operation it spells.  This text is the contract; the kernels are held to its bits.
+ * fused loss-and-gradient pass and the fp64 fold.  Built with the flags of tests/cpu_build.py (no contraction), so
+ * every line below is the fp32 or fp64 operation it spells.  This text is the contract; the kernels are held to its bits.
  *
  * dot(w, x):  acc = +0; for d0 = 0, 16, .. < round_up(dim, 16), j = 0..3, k = 0..3, d = d0 + 4 k + j:
  *             acc = fmaf(x[d], w[d], acc), both read as 0 at d >= dim (n2v_score_tile.h's chain).

@@ -1,5 +1,5 @@
 /* CPU restatement of node2vec_amd/csrc/n2v_pairs.hip: the pair score in the kernel's fixed order and the
- * four edge features.  Built by tests/test_linkpred_host.py with -ffp-contract=off, so every line below is
+ * four edge features.  Built with the flags of tests/cpu_build.py (no contraction), so every line below is
  * the fp32 operation it spells.
  *
  * The order of a dot product of `dim` elements (it depends on dim alone):

@@ -1,24 +1,19 @@
 """Shared by tests/test_cluster_host.py and tests/test_cluster_gpu.py: the CPU restatement of
 csrc/n2v_kmeans.hip (tests/cpu_kmeans/n2v_kmeans_cpu.c) behind numpy, and the case builders."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import cpu_build
 from pairs_cases import same_bits  # noqa: F401  (bit for bit, a NaN equals any NaN)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 METRICS = {"euclidean": 0, "cosine": 1}
 P = C.c_void_p
 
 
 def build(out_dir) -> C.CDLL:
-    """the restatement, compiled without contraction: one rounding per spelled operation"""
-    out = os.path.join(str(out_dir), "libn2v_kmeans_cpu.so")
-    subprocess.check_call(["cc", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-std=c11",
-                           "-o", out, os.path.join(HERE, "cpu_kmeans", "n2v_kmeans_cpu.c"), "-lm"])
-    L = C.CDLL(out)
+    """the restatement, compiled by cpu_build (no contraction: one rounding per spelled operation)"""
+    L = cpu_build.build("cpu_kmeans/n2v_kmeans_cpu.c", out_dir)
     L.n2v_kmeans_cpu_dot.restype = C.c_float
     L.n2v_kmeans_cpu_dot.argtypes = [P, P, C.c_int32]
     L.n2v_kmeans_cpu_sumsq.restype = C.c_float

@@ -2,21 +2,17 @@
 csrc/n2v_logreg.hip (tests/cpu_logreg/n2v_logreg_cpu.c) behind numpy, a float64 numpy reference (loss, gradient, a
 per-class Newton solver) and the case builders."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import cpu_build
+
 P = C.c_void_p
 
 
 def build(out_dir) -> C.CDLL:
-    """the restatement, compiled without contraction: one rounding per spelled operation"""
-    out = os.path.join(str(out_dir), "libn2v_logreg_cpu.so")
-    subprocess.check_call(["cc", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-std=c11",
-                           "-o", out, os.path.join(HERE, "cpu_logreg", "n2v_logreg_cpu.c"), "-lm"])
-    L = C.CDLL(out)
+    """the restatement, compiled by cpu_build (no contraction: one rounding per spelled operation)"""
+    L = cpu_build.build("cpu_logreg/n2v_logreg_cpu.c", out_dir)
     L.n2v_logreg_cpu_exp_neg.restype = C.c_float
     L.n2v_logreg_cpu_exp_neg.argtypes = [C.c_float]
     L.n2v_logreg_cpu_log1p01.restype = C.c_float

@@ -1,22 +1,18 @@
 """Shared by tests/test_linkpred_host.py and tests/test_linkpred_gpu.py: the CPU restatement of
 csrc/n2v_pairs.hip (tests/cpu_pairs/n2v_pairs_cpu.c) behind numpy, and the comparisons the two files make."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import cpu_build
+
 OPS = {"average": 0, "hadamard": 1, "l1": 2, "l2": 3}
 METRICS = {"dot": 0, "cosine": 1}
 
 
 def build(out_dir) -> C.CDLL:
-    """the restatement, compiled with the oracle's flags (no contraction: one rounding per spelled operation)"""
-    out = os.path.join(str(out_dir), "libn2v_pairs_cpu.so")
-    subprocess.check_call(["cc", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-std=c11",
-                           "-o", out, os.path.join(HERE, "cpu_pairs", "n2v_pairs_cpu.c"), "-lm"])
-    L = C.CDLL(out)
+    """the restatement, compiled by cpu_build (no contraction: one rounding per spelled operation)"""
+    L = cpu_build.build("cpu_pairs/n2v_pairs_cpu.c", out_dir)
     L.n2v_pairs_cpu_dot.restype = C.c_float
     L.n2v_pairs_cpu_dot.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     L.n2v_pairs_cpu_scores.restype = None

@@ -4,15 +4,14 @@ products, hand-made sentences whose result can be written down, the constructor 
 Node2VecHIP / SgnsModel, the argument checks of n2v_cbow_train, and the integer replay
 tests/cbow_groups.py (which rows a position touches) against the restatement's own counters."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pandas as pd
 import pytest
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import cpu_build
+
 M64 = (1 << 64) - 1
 
 
@@ -28,11 +27,8 @@ def lib():
 
 @pytest.fixture(scope="session")
 def cbow_cpu(tmp_path_factory):
-    """the CPU restatement, built once per session with the flags of tests/cpu_hs/n2v_hs_cpu.c"""
-    out = str(tmp_path_factory.mktemp("cbow_cpu") / "libn2v_cbow_cpu.so")
-    subprocess.check_call(["cc", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-std=c11",
-                           "-o", out, os.path.join(HERE, "cpu_cbow", "n2v_cbow_cpu.c"), "-lm"])
-    L = C.CDLL(out)
+    """the CPU restatement, built once per session by cpu_build"""
+    L = cpu_build.build("cpu_cbow/n2v_cbow_cpu.c", tmp_path_factory.mktemp("cbow_cpu"))
     L.n2v_cbow_cpu_train.restype = C.c_int64
     L.n2v_cbow_cpu_train.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32,

@@ -152,7 +152,7 @@ def _step(X, inv, Cm, metric, labels):
     out = torch.empty_like(Cm)
     counts = torch.empty(k, dtype=torch.int64, device="cuda")
     stats = torch.empty(2, dtype=torch.int64, device="cuda")
-    ws = cluster._workspace(n, dim, k, X.device)
+    ws = cluster.alloc_workspace(n, dim, k, X.device)
     _lib.check(L.n2v_kmeans_step(X.data_ptr(), None if inv is None else inv.data_ptr(), n, dim, Cm.data_ptr(), k,
                                  cluster.METRICS[metric], labels.data_ptr(), dist.data_ptr(), out.data_ptr(),
                                  counts.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(),

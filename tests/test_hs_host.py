@@ -4,7 +4,6 @@ pure-Python restatement of word2vec.c CreateBinaryTree, the CPU restatement of t
 a sequential loop, the C ABI's argument checks, and the host logic of Node2VecSpark."""
 import ctypes as C
 import os
-import subprocess
 import time
 from fractions import Fraction
 
@@ -13,9 +12,9 @@ import pandas as pd
 import pytest
 import torch
 
+import cpu_build
 from conftest import ROOT
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="session")
@@ -30,11 +29,8 @@ def lib():
 
 @pytest.fixture(scope="session")
 def hs_cpu(tmp_path_factory):
-    """the CPU restatement, built once per session with the oracle's flags"""
-    out = str(tmp_path_factory.mktemp("hs_cpu") / "libn2v_hs_cpu.so")
-    subprocess.check_call(["cc", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-std=c11",
-                           "-o", out, os.path.join(HERE, "cpu_hs", "n2v_hs_cpu.c"), "-lm"])
-    L = C.CDLL(out)
+    """the CPU restatement, built once per session by cpu_build"""
+    L = cpu_build.build("cpu_hs/n2v_hs_cpu.c", tmp_path_factory.mktemp("hs_cpu"))
     L.n2v_hs_cpu_train.restype = C.c_int64
     L.n2v_hs_cpu_train.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int32, C.c_int32,

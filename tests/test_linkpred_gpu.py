@@ -144,6 +144,27 @@ def test_special_values_pass_through_the_operators(pairs_cpu):
         assert pc.same_bits(got, pc.scores(pairs_cpu, X, None, a, b, "dot")), dim
 
 
+def test_a_base_off_the_16_byte_grid_takes_the_element_path(wanted):
+    """dim % 4 == 0, but X, or the features' out alone, starts 4 bytes past a 16-byte boundary: the same bits"""
+    from node2vec_amd import linkpred
+
+    def shifted(shape):
+        out = torch.empty(shape[0] * shape[1] + 1, device="cuda")[1:].view(shape)
+        assert out.data_ptr() % 16 == 4
+        return out
+
+    a, b, get = wanted
+    X, Xd, inv, want = get(64)
+    Xs = shifted(X.shape).copy_(Xd)
+    for metric in ("dot", "cosine"):
+        got = linkpred.pair_scores(Xs, a[:257], b[:257], metric, inv_norm=inv)
+        assert pc.same_bits(got.cpu().numpy(), want[metric][:257]), metric
+    feat = pc.numpy_features(X, a[:257], b[:257], "l2")
+    for M, out in ((Xs, None), (Xd, shifted((257, 64)))):
+        got = linkpred.pair_features(M, a[:257], b[:257], "l2", out=out)
+        assert pc.same_bits(got.cpu().numpy(), feat), out is None
+
+
 def test_offsets_past_2_31_elements(pairs_cpu):
     """rows whose first element lies beyond 2^31 floats of X (and of nothing else: X is never filled)"""
     from node2vec_amd import linkpred, similarity
