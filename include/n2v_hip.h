@@ -997,6 +997,31 @@ int n2v_logreg_loss_grad(const float *X, const uint32_t *y_bits, int64_t n, int3
                          const float *b, int32_t c, double *loss_out, double *grad_w_out, double *grad_b_out,
                          void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The moments principal components need (csrc/n2v_pca.hip, DESIGN.md "Principal components").  ADDITIONS ONLY:
+ * N2V_ABI_VERSION stays 15.  X: row-major fp32 [n, dim], 1 <= dim <= 1024, 0 <= n < 2^31; inv_norm: fp32 [n] or
+ * NULL.  Row r enters as xh[d] = x[d] * inv_norm[r] (one fp32 multiply; NULL: x[d]) and is USED when all dim values
+ * of xh are finite; every other row is skipped by both calls and not counted in n_used_out[0].  Every result is a
+ * function of the arguments alone, bit for bit (no float atomics; the orders are written out in csrc/n2v_pca.hip
+ * and restated in tests/cpu_pca/n2v_pca_cpu.c).  Argument errors are N2V_EINVAL before any launch: sizes out of
+ * range, then (n > 0) a NULL pointer, a workspace that is NULL, not 16-byte aligned or smaller than
+ * n2v_pca_workspace_bytes.  n == 0 is N2V_OK, launches nothing and writes nothing. */
+
+/* Rows per slab of both calls' fixed order of summation (a multiple of 64; -1 for sizes the calls refuse):
+ * round_up(max(1, ceil(n / S)), 64) with S = min(2048, 512 MiB / (4 round_up(dim, 16)^2)) slabs at most. */
+int64_t n2v_pca_slab_rows(int64_t n, int32_t dim);
+/* Bytes of workspace of the two calls below (-1 for sizes they refuse, 0 for n == 0): per slab an fp32
+ * [round_up(dim, 16)]^2 partial scatter, an fp64 [dim] partial sum and a count (each part rounded up to 256). */
+int64_t n2v_pca_workspace_bytes(int64_t n, int32_t dim);
+/* mean_out[d] = (sum over the used rows of (double)xh[r][d]) / n_used, fp64 [dim]; zeros when no row is used. */
+int n2v_pca_mean(const float *X, const float *inv_norm, int64_t n, int32_t dim, double *mean_out,
+                 int64_t *n_used_out, void *workspace, int64_t workspace_bytes, void *stream);
+/* scatter_out[a][b] = sum over the used rows of xc[r][a] xc[r][b], xc[r][d] = xh[r][d] - center[d] (one fp32
+ * subtraction; center fp32 [dim], NULL: uncentred), fp64 [dim, dim], symmetric to the bit: fp32 fmaf chains per
+ * slab of rows on the upper triangle, folded over the slabs in fp64 and written to both halves. */
+int n2v_pca_scatter(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *center,
+                    double *scatter_out, int64_t *n_used_out, void *workspace, int64_t workspace_bytes,
+                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -375,6 +375,43 @@ class KeyedVectors:
 
         return classify.decision_function(self._device_vectors(), result.W, result.b)
 
+    def _first_rows(self, restrict_vocab: Optional[int]) -> int:
+        n = len(self)
+        if restrict_vocab is not None:
+            if int(restrict_vocab) < 0:
+                raise ValueError("restrict_vocab must be >= 0")
+            n = min(n, int(restrict_vocab))
+        return n
+
+    def pca(self, n_components: Optional[int] = 2, metric: str = "cosine", restrict_vocab: Optional[int] = None,
+            **kw):
+        """principal components of the vectors on the GPU (node2vec_amd.pca.fit, whose other arguments pass
+        through): a PCAResult.  metric "cosine" (the default, as for kmeans) takes the rows as unit vectors over
+        the cached init_sims norms; "euclidean" takes them as trained.  restrict_vocab: only the first rows are
+        fitted."""
+        from node2vec_amd import cluster, pca
+
+        cluster.check_metric(metric)
+        n = self._first_rows(restrict_vocab)
+        pca.check_components(n_components, self.vector_size)
+        inv_norm = None
+        if metric == "cosine":
+            self.init_sims()
+            inv_norm = self._inv_norm[:n]
+        return pca.fit(self._device_vectors()[:n], n_components, unit=metric == "cosine", inv_norm=inv_norm, **kw)
+
+    def project(self, result, restrict_vocab: Optional[int] = None) -> torch.Tensor:
+        """fp32 [n, k] on the device: row i is token index2word[i] on the components of a PCAResult
+        (node2vec_amd.pca.transform); NaN for a vector that holds a non-finite value"""
+        from node2vec_amd import pca
+
+        n = self._first_rows(restrict_vocab)
+        inv_norm = None
+        if result.unit:
+            self.init_sims()
+            inv_norm = self._inv_norm[:n]
+        return pca.transform(self._device_vectors()[:n], result, inv_norm=inv_norm)
+
     @classmethod
     def load_word2vec_format(cls, fname: str) -> "KeyedVectors":
         with open(fname) as f:
@@ -526,7 +563,35 @@ class _LabelQueries:
                              "predicted": pred[:, :c].cpu().numpy().reshape(-1), "train": np.repeat(train, c)})
 
 
-class Node2VecHIP(Node2VecBase, _PairQueries, _ClusterQueries, _LabelQueries):
+class _ProjectQueries:
+    """project() of a fitted model: what Node2VecHIP and Node2VecSpark share."""
+
+    model = None
+    name_id = None
+    pca_result = None
+
+    def project(self, n_components: int = 2, metric: str = "cosine", **kw) -> pd.DataFrame:
+        """["id" | "name", "x0", "x1", ..]: every vocabulary vertex on the leading principal components of the
+        vectors, in vocabulary order (model.wv.pca and model.wv.project, whose other arguments pass through; NaN:
+        a vertex whose vector holds a non-finite value).  The default metric is cosine, as in cluster().  Names go
+        through name_id as in cluster().  The PCAResult is kept as self.pca_result."""
+        if self.model is None:
+            raise ValueError("Model is not available. Please run fit()")
+        wv = self.model.wv
+        ids = wv.ids if wv.ids is not None else np.array([int(t) for t in wv.index2word], dtype=np.int64)
+        names = None
+        if self.name_id is not None:
+            names = self.name_id.drop_duplicates("id", keep="last").set_index("id")["name"]
+            missing = ~pd.Index(ids).isin(names.index)
+            if missing.any():
+                raise KeyError(int(ids[missing][0]))
+        self.pca_result = wv.pca(n_components, metric=metric, **kw)
+        coords = wv.project(self.pca_result).cpu().numpy()
+        who = {"id": ids} if names is None else {"name": names.reindex(ids).to_numpy()}
+        return pd.DataFrame({**who, **{f"x{j}": coords[:, j] for j in range(coords.shape[1])}})
+
+
+class Node2VecHIP(Node2VecBase, _PairQueries, _ClusterQueries, _LabelQueries, _ProjectQueries):
     """Drop-in for Node2VecGensim (embedding.py:70-178) on one MI355X."""
 
     def __init__(
@@ -773,7 +838,7 @@ HIP_HS_PARAMS: Dict[str, Any] = {
 }
 
 
-class Node2VecSpark(Node2VecBase, _PairQueries, _ClusterQueries, _LabelQueries):
+class Node2VecSpark(Node2VecBase, _PairQueries, _ClusterQueries, _LabelQueries, _ProjectQueries):
     """Drop-in for the reference's Node2VecSpark (embedding.py:182-285) on one MI355X: skip-gram with
     hierarchical softmax, what Spark ML's Word2Vec trains (node2vec_amd/hs.py, csrc/n2v_hs.hip).
 
