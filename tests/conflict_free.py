@@ -151,7 +151,7 @@ def sgns_cum_table():
     return np.full(V_WORDS + 1, sgns.CUM_DOMAIN, np.int32)
 
 
-def sgns_case(oracle, dim, sentences=32, oov=False, saturated=SATURATED):
+def sgns_case(oracle, dim, sentences=32, oov=False, saturated=SATURATED, hub_rows=0, hub_cpu=None):
     """`sentences` sentences over disjoint word sets (words 1 .. 1024 dealt out at random); every
     negative is the sink word 0, whose syn1neg row [saturated, 0, ...] has f >= 6 against every syn0 row
     (syn0[:, 0] = 1, and label-1 updates only raise it).  What trains is the label-1 pair: syn0[context]
@@ -162,7 +162,12 @@ def sgns_case(oracle, dim, sentences=32, oov=False, saturated=SATURATED):
     that equals a store whenever the subtraction is exact, which Sterbenz's lemma gives while an element
     moves by less than half of itself between load and write-back.  Here a syn0 element moves by at most
     12 % of itself over a whole launch (measured under the oracle; test_train_geometry_cpu.py holds the
-    three launches together under 50 %), and a row stays cached for a few positions of one sentence."""
+    three launches together under 50 %), and a row stays cached for a few positions of one sentence.
+
+    hub_rows > 0: the case trains under the hub form instead (rows below hub_rows take atomic adds), stated
+    by the restatement `hub_cpu` (hub_form_cases.load_hub) in place of the oracle.  Those adds need not be
+    exact: what makes the launch schedule-independent is that one sentence alone adds to a row, in its own
+    order, which `prove` checks under that restatement."""
     from node2vec_amd import sgns
 
     n_vocab = V_WORDS + 1
@@ -177,21 +182,28 @@ def sgns_case(oracle, dim, sentences=32, oov=False, saturated=SATURATED):
     cum, exp = sgns_cum_table(), sgns.exp_table()
 
     def run(w, s0, s1, base, alpha):
+        if hub_rows:
+            from hub_form_cases import hub_sgns_train
+
+            return hub_sgns_train(hub_cpu, w, s0, s1, cum, None, n_vocab, base, SEED, dim, WINDOW, NEGATIVE, alpha,
+                                  hub_rows)
         return oracle.sgns_train(w, s0, s1, cum, None, exp, n_vocab, base, SEED, dim, WINDOW, NEGATIVE, alpha)
 
-    return Case(f"sgns-{dim}-{sentences}-{int(oov)}", dim, walks, m0, m1, [SINK], run)
+    return Case(f"sgns-{dim}-{sentences}-{int(oov)}" + (f"-h{hub_rows}" if hub_rows else ""), dim, walks, m0, m1,
+                [SINK], run)
 
 
 # ---- CBOW with negative sampling -----------------------------------------------------------------------------
 
-def cbow_case(cbow_cpu, dim, sentences=32, oov=False, cbow_mean=1, saturated=SATURATED, negative=NEGATIVE):
+def cbow_case(cbow_cpu, dim, sentences=32, oov=False, cbow_mean=1, saturated=SATURATED, negative=NEGATIVE,
+              hub_rows=0):
     """the corpus of sgns_case under the CBOW update: every draw of a position is the sink word 0, whose
     syn1neg row [saturated, 0, ...] has f = saturated * neu1[0] >= 6 -- neu1[0] is the sum (cbow_mean 0)
     or the mean (1) of syn0[context, 0], all 1 at the start, and only raised: the label-1 update adds
     g * neu1 with g > 0 to syn1neg[centre], so work[0] = g * syn1neg[centre, 0] >= 0.  What trains is
     syn1neg[centre] and syn0[context], words of the same sentence.  CBOW has no window cache: rows go
     back by plain stores, so syn0 takes word2vec's own initialisation.  Any `negative` does: every
-    draw is the sink."""
+    draw is the sink.  hub_rows > 0: the restatement's hub form (rows below it take atomic adds)."""
     from test_cbow_host import cpu_train
 
     n_vocab = V_WORDS + 1
@@ -207,6 +219,7 @@ def cbow_case(cbow_cpu, dim, sentences=32, oov=False, cbow_mean=1, saturated=SAT
 
     def run(w, s0, s1, base, alpha):
         return int(cpu_train(cbow_cpu, w, s0, s1, cum, None, n_vocab, base, SEED, dim, WINDOW, negative, alpha,
-                             cbow_mean))
+                             cbow_mean, hub_rows=hub_rows))
 
-    return Case(f"cbow-{dim}-{sentences}-{int(oov)}-{cbow_mean}-k{negative}", dim, walks, m0, m1, [SINK], run)
+    return Case(f"cbow-{dim}-{sentences}-{int(oov)}-{cbow_mean}-k{negative}" + (f"-h{hub_rows}" if hub_rows else ""),
+                dim, walks, m0, m1, [SINK], run)

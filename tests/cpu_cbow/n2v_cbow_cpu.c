@@ -23,12 +23,24 @@
  *   5. not cbow_mean: work *= inv;
  *   6. syn0[sent[m]] += work for the same m, ascending (a repeated word receives it twice);
  *   7. the count of trained positions grows by one.
+ * hub_rows > 0 states the kernel's hogwild HUB FORM instead (0: the above, what deterministic mode runs):
+ *   4'. a target below hub_rows takes an atomic add of the ROUNDED product,
+ *       syn1neg[target][e] = syn1neg[target][e] + fl(g * neu1[e]), where the store form has one fmaf;
+ *       work is computed from the row as it was read, as above;
+ *   6'. a context word below hub_rows takes syn0[.][e] = syn0[.][e] + work[e] as an atomic add: one fp32
+ *       addition onto what memory holds, which in order is the same value as the store.
+ * An atomic add is one fp32 addition in program order (hub_add).  Compiled with -DN2V_HUB_CHECK it counts
+ * operands that are nonzero subnormals, which a hardware fp32 atomic need not honour
+ * (n2v_cbow_cpu_subnormals); tests/test_hub_form_host.py asserts there are none.  `mutation` is test-only:
+ * 2 replaces the rounded product by fmaf, 3 treats row hub_rows itself as a hub, 4 lets the last lane
+ * that owns elements of a ragged row skip its adds (the numbering of tests/cpu_sgns_hub/n2v_sgns_hub_cpu.c).
  * Deviations from gensim, deliberate and documented (DESIGN.md "CBOW"): the draws come from the
  * project's counter-based stream where gensim runs a linear congruential generator per thread; the
  * dot product is summed in the order of the wave64 kernel (lane l owns elements l*V .. l*V+V-1,
  * then a butterfly over lane distances 1 .. 32) where BLAS sdot leaves it unspecified; the seeded
  * initialisation.  The helpers below are copied from tests/cpu_hs/n2v_hs_cpu.c.
  */
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -46,6 +58,29 @@ static inline uint64_t sentence_stream(uint64_t seed, uint64_t sentence_id) {
 
 static inline uint64_t draw(uint64_t hs, uint64_t idx) {
   return mix64(hs + (idx + 1ULL) * 0xE7037ED1A0B428DBULL);
+}
+
+static int64_t subnormal_operands = 0;
+
+/* operands of atomic adds that were nonzero subnormals since the last call; -1 without N2V_HUB_CHECK */
+int64_t n2v_cbow_cpu_subnormals(void) {
+#ifdef N2V_HUB_CHECK
+  const int64_t n = subnormal_operands;
+  subnormal_operands = 0;
+  return n;
+#else
+  (void)subnormal_operands;
+  return -1;
+#endif
+}
+
+static inline void hub_add(float *mem, float x) {
+  const float sum = *mem + x;
+#ifdef N2V_HUB_CHECK
+  subnormal_operands += (x != 0.0f && fabsf(x) < FLT_MIN) + (*mem != 0.0f && fabsf(*mem) < FLT_MIN) +
+                        (sum != 0.0f && fabsf(sum) < FLT_MIN);
+#endif
+  *mem = sum;
 }
 
 static int vec_width(int dim) {
@@ -91,11 +126,13 @@ int64_t n2v_cbow_cpu_train(const int32_t *walks, int64_t n_walks, int32_t walk_l
                            const uint32_t *cum_table, const uint32_t *sample_int, const float *exp_table,
                            int64_t n_vocab, int64_t sentence_base, uint64_t seed, int32_t dim, int32_t window,
                            int32_t negative, float alpha, const float *row_alpha, int32_t cbow_mean,
-                           int64_t *stats) {
+                           int64_t *stats, int32_t hub_rows, int32_t mutation) {
   if (walk_len < 1 || walk_len > 256 || dim < 1 || dim > 1024 || window < 1 || window > 32 || negative < 1 ||
-      negative > 32 || n_vocab < 1 || (cbow_mean != 0 && cbow_mean != 1))
+      negative > 32 || n_vocab < 1 || (cbow_mean != 0 && cbow_mean != 1) || hub_rows < 0)
     return -1;
   const int V = vec_width(dim);
+  const int hub_end = mutation == 3 ? hub_rows + 1 : hub_rows; /* rows below it are hubs */
+  const int add_end = (mutation == 4 && dim != 64 * V) ? (dim - 1) / V * V : dim;
   const uint32_t domain = cum_table[n_vocab - 1];
   int32_t sent[256], red[256];
   float *neu1 = (float *)malloc(sizeof(float) * (size_t)dim);
@@ -154,10 +191,15 @@ int64_t n2v_cbow_cpu_train(const int32_t *walks, int64_t n_walks, int32_t walk_l
         const float f = wave_dot(neu1, row2, dim, V);
         if (f <= -6.0f || f >= 6.0f) continue;
         const float g = (label - exp_table[(int)((f + 6.0f) * 83.0f)]) * a;
+        const int hub = target < hub_end;
         for (int e = 0; e < dim; ++e) {
           const float r2 = row2[e];
           work[e] = fmaf(g, r2, work[e]);
-          row2[e] = fmaf(g, neu1[e], r2);
+          if (!hub || mutation == 2) {
+            if (!hub || e < add_end) row2[e] = fmaf(g, neu1[e], r2);
+          } else if (e < add_end) {
+            hub_add(row2 + e, g * neu1[e]);
+          }
         }
       }
       if (!cbow_mean)
@@ -165,7 +207,11 @@ int64_t n2v_cbow_cpu_train(const int32_t *walks, int64_t n_walks, int32_t walk_l
       for (int m = lo; m < hi; ++m) {
         if (m == i) continue;
         float *row = syn0 + (int64_t)sent[m] * dim;
-        for (int e = 0; e < dim; ++e) row[e] = row[e] + work[e];
+        if (sent[m] < hub_end) {
+          for (int e = 0; e < add_end; ++e) hub_add(row + e, work[e]);
+        } else {
+          for (int e = 0; e < dim; ++e) row[e] = row[e] + work[e];
+        }
       }
       ++trained;
     }

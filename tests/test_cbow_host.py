@@ -25,20 +25,26 @@ def lib():
     return _lib.load()
 
 
+def cbow_argtypes():
+    """the parameters of n2v_cbow_cpu_train"""
+    return [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+            C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_void_p,
+            C.c_int32, C.c_int32]
+
+
 @pytest.fixture(scope="session")
 def cbow_cpu(tmp_path_factory):
     """the CPU restatement, built once per session by cpu_build"""
     L = cpu_build.build("cpu_cbow/n2v_cbow_cpu.c", tmp_path_factory.mktemp("cbow_cpu"))
     L.n2v_cbow_cpu_train.restype = C.c_int64
-    L.n2v_cbow_cpu_train.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32,
-                                     C.c_float, C.c_void_p, C.c_int32, C.c_void_p]
+    L.n2v_cbow_cpu_train.argtypes = cbow_argtypes()
     return L
 
 
 def cpu_train(L, walks, s0, s1, cum, sample_int, n_vocab, base, seed, dim, window, k, alpha, cbow_mean,
-              row_alpha=None, stats=None):
-    """n2v_cbow_cpu_train on numpy arrays (s0 / s1 float32, updated in place); returns the count"""
+              row_alpha=None, stats=None, hub_rows=0, mutation=0):
+    """n2v_cbow_cpu_train on numpy arrays (s0 / s1 float32, updated in place); returns the count.  hub_rows > 0:
+    the kernel's hub form (atomic adds below hub_rows); mutation: test-only, see the C file"""
     from node2vec_amd import sgns
 
     w = np.ascontiguousarray(walks, np.int32)
@@ -51,7 +57,7 @@ def cpu_train(L, walks, s0, s1, cum, sample_int, n_vocab, base, seed, dim, windo
                                 cum.ctypes.data, None if si is None else si.ctypes.data, exp.ctypes.data,
                                 n_vocab, base, seed, dim, window, k, float(alpha),
                                 None if ra is None else ra.ctypes.data, cbow_mean,
-                                None if stats is None else stats.ctypes.data)
+                                None if stats is None else stats.ctypes.data, hub_rows, mutation)
 
 
 def mix64(z):

@@ -14,17 +14,22 @@ restatement computes in order.  Each test first proves that under the restatemen
 launches with deterministic=False and the library's own wave rule and asks for the same bits.  One
 run each: the argument does not depend on scheduling.
 
-Not covered: real races (two waves on one row), and rows updated by atomic deltas -- SGNS and CBOW
-hub_rows, and the batched trainer (n2v_sgns_batched.hip), whose hogwild mode returns context rows as atomic adds
-of (row - row as loaded) and target rows as atomic adds of their deltas: their rounding differs from
-the fmaf chain of its oracle, so it has no exact many-wave test here.  The default kernel's window
-cache also writes back by atomic add; conflict_free.sgns_case keeps that add exact.
+Rows updated by atomic deltas -- SGNS and CBOW hub_rows, the window cache's write-back, and the batched
+trainer (n2v_sgns_batched.hip), whose hogwild mode returns context rows as atomic adds of (row - row as
+loaded) and hub target rows as atomic adds of their deltas -- round differently from the store form these
+restatements state.  tests/test_hub_form_gpu.py pins them bit for bit against restatements of the hub
+form: every trainer on one wave, and SGNS and CBOW hub_rows on many waves over the corpora used here.
+(The default kernel's window cache also writes back by atomic add; conflict_free.sgns_case keeps that
+add exact, so this file's store-form oracle holds for it.)
+
+Not covered: real races (two waves on one row), and the batched trainer's hogwild mode on many waves.
 """
 import numpy as np
 import pytest
 import torch
 
 import conflict_free as cf
+from same_bits import same_bits as _same_bits
 from test_cbow_host import cbow_cpu  # noqa: F401  (the session fixture that builds the CBOW restatement)
 from test_hs_host import hs_cpu  # noqa: F401  (the session fixture that builds the restatement)
 from test_train_geometry_cpu import CBOW_ALL_LANES, CBOW_DIMS, CBOW_VARIANTS, HS_DIMS, HS_VARIANTS, SGNS_VARIANTS
@@ -39,16 +44,6 @@ def _identity_vocab(n):
 
     return sgns.Vocab(torch.arange(n).cuda(), torch.full((n,), 7, dtype=torch.int64).cuda(),
                       torch.arange(n, dtype=torch.int32).cuda())
-
-
-def _same_bits(name, got, want):
-    """bit equality, and on a failure which rows and elements differ: what a fault is located from"""
-    bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-    if len(bad):
-        rows = np.unique(bad[:, 0])
-        pytest.fail(f"{name}: {len(bad)} elements in {len(rows)} rows differ; rows {rows[:16].tolist()}, "
-                    f"elements of the first {bad[bad[:, 0] == rows[0], 1][:16].tolist()}, "
-                    f"largest difference {float(np.abs(got - want).max())}", pytrace=False)
 
 
 def _compare(case, want, got0, got1, pairs, waves, exact_waves=None):
