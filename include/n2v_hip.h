@@ -576,8 +576,9 @@ int n2v_sgns_job_alpha(int32_t job_rows, int32_t epoch, int32_t epochs, int64_t 
 /* How many waves n2v_sgns_train(P, n_walks, walk_len) keeps in flight on this device (its hogwild
  * concurrency rule, max_waves and the occupancy of the kernel instance it picks, all applied) --
  * nothing is launched.  The host chooses n2v_sgns_params.hub_rows from it (node2vec_amd/sgns.py
- * auto_hub_rows: a row held by more than one wave at a time on average gets atomic adds).  0 for the
- * batched trainer; a negative status for parameters n2v_sgns_train would refuse. */
+ * auto_hub_rows: a row held by more than one wave at a time on average gets atomic adds).  With
+ * P->batched the waves of the batched trainer's launch; a negative status for parameters
+ * n2v_sgns_train would refuse. */
 int64_t n2v_sgns_hogwild_waves(const n2v_sgns_params *P, int64_t n_walks, int32_t walk_len);
 
 int n2v_sgns_train(const int32_t *walks, int64_t n_walks, int32_t walk_len,

@@ -601,7 +601,7 @@ extern "C" int n2v_sgns_batched_launch(const int32_t *walks, int64_t n_walks, in
                                        float *syn0, float *syn1neg, const uint32_t *cum_table,
                                        const uint32_t *sample_int, const float *exp_table,
                                        const n2v_sgns_params *P, unsigned long long *pairs_out,
-                                       void *stream) {
+                                       void *stream, int64_t *dry_waves) {
   using namespace n2v;
   // what the tiles hold: dim 64 / 128 / 256 (64 lanes x 1 / 2 / 4 floats), <= 15 window
   // positions + 1 in the ring (window <= 7), <= 16 target rows (negative <= 15)
@@ -625,7 +625,7 @@ extern "C" int n2v_sgns_batched_launch(const int32_t *walks, int64_t n_walks, in
   const size_t lds = kBExpTable * sizeof(float) + (size_t)wpb * per_wave;
   if (lds > 160 * 1024) return N2V_EINVAL;
   auto launch = [&](auto kernel) {
-    return launch_trainer(kernel, geo, lds, P->deterministic, pairs_out, stream, nullptr, walks, n_walks, walk_len,
+    return launch_trainer(kernel, geo, lds, P->deterministic, pairs_out, stream, dry_waves, walks, n_walks, walk_len,
                           syn0, syn1neg, cum_table, sample_int, exp_table, *P, pairs_out, own_negw);
   };
   switch (VEC) {

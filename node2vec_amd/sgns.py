@@ -201,7 +201,7 @@ class SgnsModel:
         L = _lib.load()
         P = _lib.SgnsParams(len(self.vocab), 0, self.seed, self.dim, self.window, self.negative, 0.025, 0,
                             self.cum_index_bits, 0 if self.cum_index is None else self.cum_index.data_ptr(),
-                            int(self.max_waves), 0, int(self.window_cache), 0, 0)
+                            int(self.max_waves), int(bool(self.batched)), int(self.window_cache), 0, 0)
         fn, name = ((L.n2v_sgns_hogwild_waves, "n2v_sgns_hogwild_waves") if self.sg else
                     (L.n2v_cbow_hogwild_waves, "n2v_cbow_hogwild_waves"))
         with torch.cuda.device(self.syn0.device):

@@ -3,11 +3,19 @@
 Both word2vec updates skip a node or target whose f <= -6 or f >= 6 BEFORE any store.  So a launch of
 many unsynchronised waves computes exactly what one thread computes when
   * no two sentences train the same row, and
-  * the rows every sentence must read (HS: the top of the tree; SGNS and CBOW: the negative samples)
-    are saturated, so nobody ever writes them.
+  * the rows every sentence reads (HS: the top of the tree; SGNS and CBOW: the negative samples) are
+    saturated: nobody ever changes them (the batched kernel rewrites them, with the bits they hold).
 CBOW: every target of a position other than its centre word is the sink, whose f against the summed
 (or averaged) context is >= 6; what trains is syn1neg[centre] and syn0[context], all of them words of
 one sentence.
+The batched skip-gram kernel (n2v_sgns_batched.hip) has no skip before the store: it writes EVERY target
+row of a position back, the saturated sinks included.  Schedule independence only needs that a shared row
+is never given other bits than it holds, and that is what happens: the sink's coefficients G are the
+literal 0.0f (|f| >= 6), so its store writes old + sum(0 * x) and its hub-form add puts +0 + sum(0 * x)
+onto memory.  With finite x and no -0 in the sink row both are the row's own bits: every wave stores the
+same 4-byte words over and over, and a reader sees those words under any schedule.  `prove` checks the
+first half (the shared rows keep their bits under the restatement, which performs the same stores and
+adds); tests/test_batched_geometry_host.py checks the two premises, finite values and no -0.
 `prove` checks those conditions under the CPU restatement alone; only then is a GPU comparison with
 the restatement's joint run meaningful (tests/test_train_geometry_cpu.py, test_train_geometry_gpu.py).
 
@@ -77,8 +85,12 @@ def prove(case):
     return j0, j1, pairs
 
 
-def _sentences(rng, groups, oov):
-    walks = np.stack([rng.choice(g, TOKENS) for g in groups]).astype(np.int32)
+def _sentences(rng, groups, oov, tokens=TOKENS, back=0.0):
+    walks = np.stack([rng.choice(g, tokens) for g in groups]).astype(np.int32)
+    if back:  # walk-like: a token repeats the one two places back (a b a)
+        for t in np.arange(2, tokens):
+            again = rng.random(len(groups)) < back
+            walks[again, t] = walks[again, t - 2]
     if oov:  # out-of-vocabulary tokens: dropped before windowing
         walks[rng.random(walks.shape) < 0.15] = -1
         walks[0, :3] = -1
@@ -223,3 +235,92 @@ def cbow_case(cbow_cpu, dim, sentences=32, oov=False, cbow_mean=1, saturated=SAT
 
     return Case(f"cbow-{dim}-{sentences}-{int(oov)}-{cbow_mean}-k{negative}" + (f"-h{hub_rows}" if hub_rows else ""),
                 dim, walks, m0, m1, [SINK], run)
+
+
+# ---- the batched skip-gram trainer (negatives shared by the pairs of a position) ------------------------------
+
+def batched_case(hub_cpu, dim, window, negative, sinks, sentences=32, tokens=TOKENS, oov=False, hub_rows=0,
+                 ctx_store=0):
+    """`sinks` sink words at rows 0 .. sinks - 1, then the 1024 sentence words, dealt out at random over
+    `sentences` disjoint groups.  The noise table spreads its mass evenly over the sinks, each with the
+    syn1neg row [SATURATED, 0, ...]: every negative is a sink, f >= 6 against syn0[:, 0] = 1 (which the
+    label-1 updates only raise), G = 0, and the row is rewritten with its own bits (module docstring).  One
+    sink would give every position two targets and one multiplicity; several make the number of distinct
+    targets and their multiplicities vary from position to position, which the target tile, the packed
+    multiplicity words and the `late` masks need.
+
+    syn0 takes word2vec's ordinary initialisation (column 0 apart): the ring's write-back add
+    loaded + (t - loaded) then differs in bits from a store of t on some elements, so a kernel that stores
+    where it should add fails (with magnitudes kept away from zero the two agree everywhere).  Sentences are
+    walk-like -- about 30 % of the tokens from index 2 on repeat the token two places back -- so the window
+    holds a word at several positions: shared ring rows, multiplicities > 1.
+
+    The run is the hub restatement's (hub_form_cases.hub_batched_train) under hub_rows and ctx_store
+    (1: context rows go back as stores, the deterministic form -- the twin a hogwild launch must differ from)."""
+    from hub_form_cases import hub_batched_train
+    from node2vec_amd import sgns
+
+    n_vocab = V_WORDS + sinks
+    rng = np.random.default_rng([4000, dim, window, negative, sinks, sentences, tokens, int(oov)])
+    words = sinks + rng.permutation(V_WORDS)
+    groups = np.split(words, sentences)
+    m0 = _syn0(rng, n_vocab, dim, away_from_zero=False)
+    m1 = np.zeros((n_vocab, dim), np.float32)
+    m1[:sinks, 0] = SATURATED
+    walks = _sentences(rng, groups, oov, tokens, back=0.3)
+    assert walks.min() >= (-1 if oov else sinks)
+    cum = np.full(n_vocab, sgns.CUM_DOMAIN, np.int64)
+    cum[:sinks] = (np.arange(sinks) + 1) * sgns.CUM_DOMAIN // sinks
+    cum = cum.astype(np.int32)
+
+    def run(w, s0, s1, base, alpha):
+        return hub_batched_train(hub_cpu, w, s0, s1, cum, None, n_vocab, base, SEED, dim, window, negative, alpha,
+                                 hub_rows, ctx_store)
+
+    name = f"batched-{dim}-w{window}-k{negative}-s{sinks}-{sentences}x{tokens}-{int(oov)}-h{hub_rows}-c{ctx_store}"
+    return Case(name, dim, walks, m0, m1, np.arange(sinks), run,
+                {"cum": cum, "n_vocab": n_vocab, "window": window, "negative": negative, "sinks": sinks})
+
+
+_M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
+
+
+def _mix64(z):
+    """splitmix64's finaliser over a uint64 array (numpy's uint64 products wrap)"""
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def batched_plans(case):
+    """What the batched trainer's plan holds for every (launch, sentence, kept position) of the case,
+    restated in plain numpy from the trainers' draw streams: sentence stream mix64(seed ^ mix64(id + c0)),
+    draw idx -> mix64(stream + (idx + 1) * c1), negative d of kept position i at idx 2 * walk_len +
+    i * 2 * window * negative + d, word = bisect_left(cum, (draw >> 16) % domain); targets = the centre,
+    then the distinct draws other than it.  Returns (distinct targets per position, largest multiplicity
+    per position, nf per sentence) as three flat lists."""
+    cum = case.extra["cum"].view(np.uint32)
+    window, negative = case.extra["window"], case.extra["negative"]
+    walk_len = case.walks.shape[1]
+    domain = np.uint64(cum[-1])
+    n_targets, max_mult, nfs = [], [], []
+    with np.errstate(over="ignore"):
+        for base, _ in case.launches():
+            for r, row in enumerate(case.walks):
+                sent = row[(row >= 0) & (row < case.extra["n_vocab"])]
+                nfs.append(len(sent))
+                if len(sent) < 2:
+                    continue
+                sid = np.array([base + r], np.uint64)
+                hs = _mix64(np.uint64(SEED) ^ _mix64(sid + np.uint64(0xA0761D6478BD642F)))
+                i = np.arange(len(sent), dtype=np.uint64)[:, None]
+                d = np.arange(negative, dtype=np.uint64)[None, :]
+                idx = np.uint64(2 * walk_len) + i * np.uint64(2 * window * negative) + d
+                x = (_mix64(hs + (idx + np.uint64(1)) * np.uint64(0xE7037ED1A0B428DB)) >> np.uint64(16)) % domain
+                word = np.searchsorted(cum, x.astype(np.uint32), side="left")
+                for c, ws in zip(sent, word):
+                    ws = ws[ws != c]
+                    _, counts = np.unique(ws, return_counts=True)
+                    n_targets.append(1 + len(counts))
+                    max_mult.append(int(counts.max()) if len(counts) else 1)
+    return n_targets, max_mult, nfs

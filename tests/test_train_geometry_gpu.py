@@ -22,7 +22,11 @@ form: every trainer on one wave, and SGNS and CBOW hub_rows on many waves over t
 (The default kernel's window cache also writes back by atomic add; conflict_free.sgns_case keeps that
 add exact, so this file's store-form oracle holds for it.)
 
-Not covered: real races (two waves on one row), and the batched trainer's hogwild mode on many waves.
+The batched trainer's hogwild mode on many waves has a file of its own, tests/test_batched_geometry_gpu.py:
+its kernel rewrites the saturated sink rows at every position, so it runs under the weaker precondition
+that a shared row only ever receives the bits it holds (tests/conflict_free.py).
+
+Not covered: real races (two waves on one row), which stay a statistical claim.
 """
 import numpy as np
 import pytest
@@ -95,7 +99,7 @@ SGNS_CONFIGS = [(64, 0), (128, 0), (200, 0), (512, 0), (64, 1), (128, 1)]
 @pytest.mark.parametrize("dim,window_cache", SGNS_CONFIGS)
 def test_sgns_hogwild_bit_identical_on_conflict_free_corpus(oracle, dim, window_cache, sentences, oov):
     """the default kernel, plain stores everywhere (hub_rows = 0, sample = 0).  64 sentences run on 16
-    waves.  The batched trainer is left out: see the module docstring."""
+    waves.  The batched trainer: tests/test_batched_geometry_gpu.py (see the module docstring)."""
     from node2vec_amd import _lib, sgns
 
     case = cf.sgns_case(oracle, dim, sentences, oov)
