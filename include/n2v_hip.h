@@ -1023,6 +1023,36 @@ int n2v_pca_scatter(const float *X, const float *inv_norm, int64_t n, int32_t di
                     double *scatter_out, int64_t *n_used_out, void *workspace, int64_t workspace_bytes,
                     void *stream);
 
+/* Approximate nearest neighbours over an inverted-file (IVF-flat) index of X (csrc/n2v_ivf.hip, DESIGN.md
+ * "Approximate nearest neighbours").  ADDITIONS ONLY: N2V_ABI_VERSION stays 15.  The index is device data over X in
+ * place: list_off int64 [nlist + 1] and row_ids int32 [list_off[nlist]], the rows of X in list order (ascending
+ * inside a list); max_list_rows >= the longest list.  probes: int32 [n_queries, nprobe], for every query the lists
+ * it scans, -1 for an unused slot; the entries of a query must be distinct.  A query's candidates are the rows of
+ * its probed lists; out_rows / out_scores [n_queries, k] are the k best of them, every score equal to
+ * n2v_knn_scores' of the same (query, row) bit for bit, by score descending, then row number ascending; a NaN score
+ * is never selected; the tail is row -1, score -inf.  Nothing else is approximate: with every list probed the
+ * result is n2v_knn_topk's.  Bounds: X as n2v_knn_*; 1 <= nlist <= 1024; 1 <= nprobe <= nlist; 1 <= k <= 128;
+ * 1 <= max_list_rows <= n; n_queries < 2^20; exactly one of queries / query_rows non-NULL.  Argument errors are
+ * N2V_EINVAL before any launch; n == 0 or n_queries == 0 is N2V_OK and launches nothing.  A list longer than
+ * max_list_rows, offsets that descend, a probe outside [-1, nlist) or a row id outside [0, n) sets N2V_ST_RANGE in
+ * status[0] (a device word, read after synchronising): the call still runs, reads nothing out of bounds, and its
+ * results must be discarded. */
+
+/* Bytes of workspace n2v_ivf_topk needs; -1 for sizes it refuses (also: more scan blocks than one launch takes --
+ * split the queries), 0 for n == 0 or n_queries == 0.  Non-decreasing in n_queries, nprobe and k. */
+int64_t n2v_ivf_workspace_bytes(int64_t n, int32_t dim, int32_t nlist, int64_t max_list_rows, int64_t n_queries,
+                                int32_t nprobe, int32_t k);
+/* The launch shape, for tests (host memory): plan3 = {(query, probe) pairs per tile: 16 or 64, rows per chunk of a
+ * list: a multiple of 128, chunks per list = ceil(max_list_rows / rows per chunk)}. */
+int n2v_ivf_plan(int64_t n, int32_t dim, int32_t nlist, int64_t max_list_rows, int64_t n_queries, int32_t nprobe,
+                 int32_t k, int64_t *plan3);
+/* workspace: 16-byte aligned, workspace_bytes >= n2v_ivf_workspace_bytes. */
+int n2v_ivf_topk(const float *X, const float *inv_norm, int64_t n, int32_t dim, const int64_t *list_off,
+                 const int32_t *row_ids, int32_t nlist, int64_t max_list_rows, const float *queries,
+                 const int64_t *query_rows, int64_t n_queries, const int32_t *probes, int32_t nprobe, int32_t k,
+                 int64_t *out_rows, float *out_scores, uint32_t *status, void *workspace, int64_t workspace_bytes,
+                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

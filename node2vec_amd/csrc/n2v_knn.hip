@@ -10,20 +10,11 @@
 // (score_tile: a k-ordered fmaf chain, element by element).  Nothing depends on the number of queries,
 // the tile a row or a query lands in, or the entry point: the fused top-k kernel and the full-score
 // kernel call the same score_tile, so n2v_knn_topk's scores equal n2v_knn_scores' bit for bit.
-#include <float.h>
-
-#include "n2v_score_tile.h"
+#include "n2v_topk_select.h"
 
 namespace {
 
-constexpr int kWaves = 8;              // waves per block of the top-k kernel
-constexpr int kStepRows = kWaves * 16; // rows scored per block step (16 per wave)
-constexpr int kMaxK = 1024;            // the fused path's k limit
-constexpr int kSentinelRow = 0x7fffffff;
-
-// the padded query matrix q_hat [nq_pad][dim_pad] at the start of the workspace (zeros in the padding):
-// a tile of G x 16 queries starting at any multiple of its 8, 16, 32 or 64 kept queries stays inside
-inline int64_t nq_pad_of(int64_t nq) { return round_up(nq, 64) + 16; }
+constexpr int kMaxK = 1024;  // the fused path's k limit
 
 __global__ __launch_bounds__(256) void inv_norm_kernel(const float *__restrict__ X, int64_t n, int32_t dim,
                                                        float *__restrict__ inv_norm) {
@@ -34,36 +25,6 @@ __global__ __launch_bounds__(256) void inv_norm_kernel(const float *__restrict__
     if (lane == 0) inv_norm[r] = inv_sqrt_or_zero(s);
   }
 }
-
-// q_hat of every query into the workspace; a query given as row r uses inv_norm[r] itself
-__global__ __launch_bounds__(256) void queries_kernel(const float *__restrict__ X, const float *__restrict__ inv_norm,
-                                                      int32_t dim, const float *__restrict__ queries,
-                                                      const int64_t *__restrict__ query_rows, int64_t nq,
-                                                      int64_t nq_pad, float *__restrict__ qhat) {
-  const int lane = threadIdx.x & 63;
-  const int32_t dp = dim_pad_of(dim);
-  const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (q >= nq_pad) return;
-  float *out = qhat + q * dp;
-  if (q >= nq) {
-    for (int d = lane; d < dp; d += 64) out[d] = 0.f;
-    return;
-  }
-  const float *v;
-  float inv;
-  if (query_rows) {
-    const int64_t r = query_rows[q];
-    v = X + r * dim;
-    inv = inv_norm[r];
-  } else {
-    v = queries + q * dim;
-    inv = inv_sqrt_or_zero(wave_sumsq(v, dim, lane));
-  }
-  for (int d = lane; d < dp; d += 64) out[d] = d < dim ? v[d] * inv : 0.f;
-}
-
-// the order of results: score descending, then row ascending (empty slots: -inf, kSentinelRow)
-__device__ inline bool better(float sa, int ra, float sb, int rb) { return sa > sb || (sa == sb && ra < rb); }
 
 // Every score of 16 queries against 16 rows per wave (grid: x = row tiles of 64, y = query tiles of 16)
 template <bool VEC>
@@ -86,71 +47,22 @@ __global__ __launch_bounds__(256) void scores_kernel(const float *__restrict__ X
 }
 
 // Fused scan: block (x = query tile, y = chunk of rows) keeps, for each of its QACT queries, the best
-// candidates of its chunk in an LDS buffer of CAP entries.  A score below the query's threshold (the
-// k-th best kept so far) costs one compare; the others are appended.  When a buffer could overflow in
-// the next step every buffer is sorted (bitonic, by `better`) and cut to k.  At the end the sorted
+// candidates of its chunk in an LDS buffer of CAP entries (TopkBuffers, n2v_topk_select.h).  At the end the sorted
 // top k of the chunk go to part[q][chunk][0..k).  G groups of 16 queries are scored, the first QACT kept.
 template <int G, int QACT, int CAP, bool VEC>
 __global__ __launch_bounds__(kWaves * 64) void topk_chunk_kernel(
     const float *__restrict__ X, const float *__restrict__ inv_norm, int64_t n, int32_t dim,
     const float *__restrict__ qhat, int64_t nq, int32_t k, int64_t chunk_rows, int32_t n_chunks,
     float *__restrict__ part_s, int32_t *__restrict__ part_r) {
-  __shared__ float buf_s[QACT][CAP];
-  __shared__ int32_t buf_r[QACT][CAP];
-  __shared__ int32_t cnt[QACT];
-  __shared__ float thr[QACT];
-  __shared__ int32_t need_sort;
+  __shared__ TopkBuffers<QACT, CAP> buf;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t q0 = (int64_t)blockIdx.x * QACT;
   const int32_t chunk = blockIdx.y;
   const int64_t lo = (int64_t)chunk * chunk_rows;
   const int64_t hi = lo + chunk_rows < n ? lo + chunk_rows : n;
-  for (int i = tid; i < QACT * CAP; i += kWaves * 64) {
-    buf_s[i / CAP][i % CAP] = -INFINITY;
-    buf_r[i / CAP][i % CAP] = kSentinelRow;
-  }
-  for (int i = tid; i < QACT; i += kWaves * 64) {
-    cnt[i] = 0;
-    thr[i] = -INFINITY;
-  }
-  if (tid == 0) need_sort = 0;
-  __syncthreads();
-
-  auto sort_all = [&]() {
-    // bitonic sort of every buffer, best first; slots past cnt hold (-inf, sentinel)
-    for (int size = 2; size <= CAP; size <<= 1) {
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        for (int p = tid; p < QACT * (CAP / 2); p += kWaves * 64) {
-          const int q = p / (CAP / 2), j = p % (CAP / 2);
-          const int a = 2 * j - (j & (stride - 1)), b = a + stride;
-          const bool up = (a & size) == 0;  // this half sorted best first
-          const float sa = buf_s[q][a], sb = buf_s[q][b];
-          const int ra = buf_r[q][a], rb = buf_r[q][b];
-          if (better(sb, rb, sa, ra) == up) {
-            buf_s[q][a] = sb, buf_s[q][b] = sa;
-            buf_r[q][a] = rb, buf_r[q][b] = ra;
-          }
-        }
-        __syncthreads();
-      }
-    }
-    // keep k: the rest becomes empty again; the k-th kept score is the new threshold
-    for (int i = tid; i < QACT * CAP; i += kWaves * 64) {
-      const int q = i / CAP, j = i % CAP;
-      if (j >= k && j < cnt[q]) {
-        buf_s[q][j] = -INFINITY;
-        buf_r[q][j] = kSentinelRow;
-      }
-    }
-    __syncthreads();
-    for (int q = tid; q < QACT; q += kWaves * 64) {
-      if (cnt[q] >= k) thr[q] = buf_s[q][k - 1];
-      cnt[q] = cnt[q] < k ? cnt[q] : k;
-    }
-    if (tid == 0) need_sort = 0;
-    __syncthreads();
-  };
+  const int q_live = nq - q0 < QACT ? (int)(nq - q0) : QACT;
+  topk_reset(buf, tid);
 
   const float *qtile = qhat + q0 * dim_pad_of(dim);
   for (int64_t base = lo; base < hi; base += kStepRows) {
@@ -159,96 +71,26 @@ __global__ __launch_bounds__(kWaves * 64) void topk_chunk_kernel(
       f32x4 acc[G];
       score_tile<G, VEC>(X, dim, row0, hi, qtile, lane, acc);
       float inv[4];
+      int32_t row[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int64_t r = row0 + 4 * (lane >> 4) + i;
+        row[i] = r < hi ? (int32_t)r : -1;
         inv[i] = r < hi ? inv_norm[r] : 0.f;
       }
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const int q = 16 * g + (lane & 15);
-        if (q >= QACT || q0 + q >= nq) continue;
-        const float t = thr[q];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int64_t r = row0 + 4 * (lane >> 4) + i;
-          const float s = acc[g][i] * inv[i];
-          // a tie with the threshold cannot win (its row is above every kept row: rows arrive in ascending
-          // order within a chunk), so s >= t keeps nothing s > t would not need; NaN fails both
-          if (r < hi && s >= t) {
-            const int pos = atomicAdd(&cnt[q], 1);
-            buf_s[q][pos] = s;
-            buf_r[q][pos] = (int32_t)r;
-            if (pos >= CAP - kStepRows) need_sort = 1;
-          }
-        }
-      }
+      topk_offer<G>(buf, acc, inv, row, q_live, lane);
     }
     __syncthreads();
-    if (need_sort) sort_all();
+    if (buf.need_sort) topk_sort_cut(buf, k, tid);
   }
-  sort_all();
+  topk_sort_cut(buf, k, tid);
   for (int i = tid; i < QACT * k; i += kWaves * 64) {
     const int q = i / k, j = i % k;
     if (q0 + q >= nq) continue;
     const int64_t o = ((q0 + q) * n_chunks + chunk) * (int64_t)k + j;
-    part_s[o] = buf_s[q][j];
-    part_r[o] = buf_r[q][j];
+    part_s[o] = buf.s[q][j];
+    part_r[o] = buf.r[q][j];
   }
-}
-
-// rank of (s, r) among the k sorted entries of a list: how many are better
-__device__ inline int rank_in(const float *__restrict__ ls, const int32_t *__restrict__ lr, int k, float s, int r) {
-  int a = 0, b = k;
-  while (a < b) {
-    const int m = (a + b) >> 1;
-    if (better(ls[m], lr[m], s, r)) a = m + 1;
-    else b = m;
-  }
-  return a;
-}
-
-// One block per query: the n_chunks sorted lists of k are merged pairwise (log2 rounds, ping-pong
-// between the two halves of the workspace); an entry's place in a merged pair is its own index plus its
-// rank in the other list (rows are unique, the empty slots identical).  The winner goes to out.
-__global__ __launch_bounds__(256) void merge_kernel(float *__restrict__ s0, int32_t *__restrict__ r0,
-                                                    float *__restrict__ s1, int32_t *__restrict__ r1,
-                                                    int32_t n_chunks, int32_t k, int64_t *__restrict__ out_rows,
-                                                    float *__restrict__ out_scores) {
-  const int64_t q = blockIdx.x;
-  const int64_t span = (int64_t)n_chunks * k;
-  float *src_s = s0 + q * span, *dst_s = s1 + q * span;
-  int32_t *src_r = r0 + q * span, *dst_r = r1 + q * span;
-  for (int32_t lists = n_chunks; lists > 1; lists = (lists + 1) / 2) {
-    const int32_t pairs = lists / 2;
-    for (int64_t e = threadIdx.x; e < (int64_t)lists * k; e += blockDim.x) {
-      const int32_t l = (int32_t)(e / k), i = (int32_t)(e % k);
-      const float s = src_s[e];
-      const int32_t r = src_r[e];
-      int32_t pos = i, dst_list = l / 2;
-      if (l < 2 * pairs) {
-        const int32_t other = l ^ 1;
-        pos += rank_in(src_s + (int64_t)other * k, src_r + (int64_t)other * k, k, s, r);
-      }
-      if (pos < k) {
-        dst_s[(int64_t)dst_list * k + pos] = s;
-        dst_r[(int64_t)dst_list * k + pos] = r;
-      }
-    }
-    __syncthreads();
-    float *ts = src_s; src_s = dst_s; dst_s = ts;
-    int32_t *tr = src_r; src_r = dst_r; dst_r = tr;
-  }
-  for (int i = threadIdx.x; i < k; i += blockDim.x) {
-    const int32_t r = src_r[i];
-    out_rows[q * k + i] = r == kSentinelRow ? -1 : r;
-    out_scores[q * k + i] = r == kSentinelRow ? -INFINITY : src_s[i];
-  }
-}
-
-// q_hat, the first piece of every workspace
-float *take_qhat(Carver &carve, int32_t dim, int64_t nq) {
-  return carve.take<float>(nq_pad_of(nq) * dim_pad_of(dim) * 4);
 }
 
 // the launch shape of n2v_knn_topk: query tile, LDS buffer, chunks; and the workspace `ws` laid out (ws null: only
@@ -289,23 +131,6 @@ TopkPlan plan_topk(int64_t n, int32_t dim, int64_t nq, int32_t k, void *ws) {
   return p;
 }
 
-bool args_ok(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *queries,
-             const int64_t *query_rows, int64_t nq) {
-  if (!matrix_ok(n, dim) || nq < 0) return false;
-  if ((queries == nullptr) == (query_rows == nullptr)) return false;
-  if (!X || !inv_norm) return false;
-  return true;
-}
-
-int launch_queries(const float *X, const float *inv_norm, int32_t dim, const float *queries,
-                   const int64_t *query_rows, int64_t nq, float *qhat, hipStream_t st) {
-  const int64_t nq_pad = nq_pad_of(nq);
-  hipLaunchKernelGGL(queries_kernel, dim3((unsigned)((nq_pad + 3) / 4)), dim3(256), 0, st, X, inv_norm, dim,
-                     queries, query_rows, nq, nq_pad, qhat);
-  N2V_HIP_CHECK(hipGetLastError());
-  return N2V_OK;
-}
-
 template <int G, int QACT, int CAP>
 void launch_topk(const TopkPlan &p, const float *X, const float *inv_norm, int64_t n, int32_t dim, int64_t nq,
                  int32_t k, hipStream_t st) {
@@ -343,7 +168,7 @@ int64_t n2v_knn_workspace_bytes(int64_t n, int32_t dim, int64_t n_queries, int32
 int n2v_knn_topk(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *queries,
                  const int64_t *query_rows, int64_t n_queries, int32_t k, int64_t *out_rows, float *out_scores,
                  void *workspace, int64_t workspace_bytes, void *stream) {
-  if (!args_ok(X, inv_norm, n, dim, queries, query_rows, n_queries)) return N2V_EINVAL;
+  if (!query_args_ok(X, inv_norm, n, dim, queries, query_rows, n_queries)) return N2V_EINVAL;
   if (k < 1 || k > kMaxK) return N2V_EINVAL;
   if (n == 0 || n_queries == 0) return N2V_OK;
   const TopkPlan p = plan_topk(n, dim, n_queries, k, workspace);
@@ -367,7 +192,7 @@ int n2v_knn_topk(const float *X, const float *inv_norm, int64_t n, int32_t dim, 
 int n2v_knn_scores(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *queries,
                    const int64_t *query_rows, int64_t n_queries, float *out_scores, void *workspace,
                    int64_t workspace_bytes, void *stream) {
-  if (!args_ok(X, inv_norm, n, dim, queries, query_rows, n_queries)) return N2V_EINVAL;
+  if (!query_args_ok(X, inv_norm, n, dim, queries, query_rows, n_queries)) return N2V_EINVAL;
   if (n == 0 || n_queries == 0) return N2V_OK;
   Carver carve(workspace);
   float *qhat = take_qhat(carve, dim, n_queries);

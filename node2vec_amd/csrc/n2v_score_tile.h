@@ -1,7 +1,8 @@
-// n2v_score_tile.h -- the fixed-order fp32 pieces n2v_knn.hip, n2v_kmeans.hip and n2v_logreg.hip share: the sum of
-// squares of a row (wave_sumsq), 1 / sqrt or 0, the 16 x 16 MFMA dot chain (score_tile) and the kernel that pads
-// its operand B (pad_rows_kernel).  Every caller gets the same bits from the same code (DESIGN.md "Nearest
-// neighbours", "Clustering", "Node classification"); what surrounds the kernels on the host is n2v_dense_host.h.
+// n2v_score_tile.h -- the fixed-order fp32 pieces n2v_knn.hip, n2v_ivf.hip, n2v_kmeans.hip and n2v_logreg.hip share:
+// the sum of squares of a row (wave_sumsq), 1 / sqrt or 0, the 16 x 16 MFMA dot chain (score_rows, and score_tile
+// over contiguous operands) and the kernel that pads its operand B (pad_rows_kernel).  Every caller gets the same
+// bits from the same code (DESIGN.md "Nearest neighbours", "Clustering", "Node classification"); what surrounds the
+// kernels on the host is n2v_dense_host.h.
 #pragma once
 
 #include "n2v_dense_host.h"
@@ -50,20 +51,17 @@ void launch_pad_rows(hipStream_t st, const float *src, int32_t n_rows, int64_t r
                      dim, dst, sumsq);
 }
 
-// Dot products of 16 rows (row0 ..) with G groups of 16 queries, one wave: acc[g][i] is
-// dot(q_hat[16 g + (lane & 15)], x[row0 + 4 (lane >> 4) + i]).  The X tile is operand A (lane l:
-// row l & 15, k = l >> 4), q_hat operand B (query l & 15, k = l >> 4); a lane loads d0 + 4 k .. + 3 and
-// feeds them to four MFMAs, so d is summed in the order d0 + 4 k + j over (d0, j, k) -- fixed.
-// Rows at or beyond `row_end` and dims at or beyond `dim` read as 0.
+// Dot products of 16 rows with G groups of 16 queries, one wave: acc[g][i] is dot(query 16 g + (lane & 15),
+// row 4 (lane >> 4) + i of the tile).  The X tile is operand A (lane l: row l & 15, k = l >> 4), q_hat operand B
+// (query l & 15, k = l >> 4); a lane loads d0 + 4 k .. + 3 and feeds them to four MFMAs, so d is summed in the
+// order d0 + 4 k + j over (d0, j, k) -- fixed.  Both sides are given per lane, so either may be gathered: `xr`
+// the lane's row of X (read as 0 when not `live`, and at dims at or beyond `dim`; it must still be a readable
+// address), qrow[g] the padded q_hat row (dim_pad floats, 16-byte aligned) of the lane's query in group g.
 template <int G, bool VEC>
-__device__ inline void score_tile(const float *__restrict__ X, int32_t dim, int64_t row0, int64_t row_end,
-                                  const float *__restrict__ qhat_tile, int lane, f32x4 (&acc)[G]) {
+__device__ inline void score_rows(const float *__restrict__ xr, bool live, int32_t dim,
+                                  const float *(&qrow)[G], int lane, f32x4 (&acc)[G]) {
   const int32_t dp = dim_pad_of(dim);
-  const int64_t row = row0 + (lane & 15);
-  const bool live = row < row_end;
-  const float *xr = X + (live ? row : 0) * (int64_t)dim;
   const int k4 = 4 * (lane >> 4);
-  const float *qb = qhat_tile + (int64_t)(lane & 15) * dp + k4;
 #pragma unroll
   for (int g = 0; g < G; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
   constexpr int kBatch = 8;  // X loads in flight per lane: 8 x 16 B
@@ -85,7 +83,7 @@ __device__ inline void score_tile(const float *__restrict__ X, int32_t dim, int6
       if (d0 >= dp) break;
 #pragma unroll
       for (int g = 0; g < G; ++g) {
-        const f32x4 q4 = *reinterpret_cast<const f32x4 *>(qb + (int64_t)g * 16 * dp + d0);
+        const f32x4 q4 = *reinterpret_cast<const f32x4 *>(qrow[g] + k4 + d0);
         acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[b].x, q4.x, acc[g], 0, 0, 0);
         acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[b].y, q4.y, acc[g], 0, 0, 0);
         acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[b].z, q4.z, acc[g], 0, 0, 0);
@@ -93,6 +91,20 @@ __device__ inline void score_tile(const float *__restrict__ X, int32_t dim, int6
       }
     }
   }
+}
+
+// score_rows over a contiguous run of rows (row0 .., rows at or beyond `row_end` read as 0) and a contiguous
+// q_hat tile [16 G][dim_pad]: acc[g][i] is dot(q_hat[16 g + (lane & 15)], x[row0 + 4 (lane >> 4) + i]).
+template <int G, bool VEC>
+__device__ inline void score_tile(const float *__restrict__ X, int32_t dim, int64_t row0, int64_t row_end,
+                                  const float *__restrict__ qhat_tile, int lane, f32x4 (&acc)[G]) {
+  const int32_t dp = dim_pad_of(dim);
+  const int64_t row = row0 + (lane & 15);
+  const bool live = row < row_end;
+  const float *qrow[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) qrow[g] = qhat_tile + (int64_t)(16 * g + (lane & 15)) * dp;
+  score_rows<G, VEC>(X + (live ? row : 0) * (int64_t)dim, live, dim, qrow, lane, acc);
 }
 
 }  // namespace

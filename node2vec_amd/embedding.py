@@ -246,14 +246,36 @@ class KeyedVectors:
         query = mean / norm if norm > 0 else mean
         return query.astype(np.float32), sorted({row for row, _, _ in parsed if row is not None})
 
+    def build_index(self, nlist: Optional[int] = None, nprobe: int = 8, seed: int = 0, **kw):
+        """An inverted-file index over the vectors for approximate queries (node2vec_amd.ann.build_index, whose other
+        arguments pass through): spherical k-means into nlist lists over the cached init_sims norms.  Hand it to
+        most_similar / similar_by_* / nearest as indexer=; its nprobe (lists scanned per query) may be set at any
+        time.  It indexes the vectors as they are now."""
+        from node2vec_amd import ann
+
+        self.init_sims()
+        return ann.build_index(self._device_vectors(), nlist=nlist, nprobe=nprobe, seed=seed,
+                               inv_norm=self._inv_norm, **kw)
+
+    @staticmethod
+    def _check_indexer(topn, restrict_vocab) -> None:
+        if restrict_vocab is not None:
+            raise ValueError("restrict_vocab cannot be combined with indexer=: the index covers every row")
+        if topn is None:
+            raise ValueError("topn=None (every score) cannot be combined with indexer=")
+
     def most_similar(self, positive=None, negative=None, topn: Optional[int] = 10,
-                     restrict_vocab: Optional[int] = None):
+                     restrict_vocab: Optional[int] = None, indexer=None):
         """gensim 3.8 KeyedVectors.most_similar: [(token, cosine)] of the topn nearest rows to the unit mean of
         weight * unit(token vector) (weight +1 for positive, -1 for negative, or given as (item, weight));
         a vector given as such enters as it is, as in gensim.  The input tokens are not returned.
         topn=None: the whole fp32 score array.  restrict_vocab: only the first rows are searched.
         A row holding inf or NaN (or a query that does) scores NaN: it is never returned, for every topn, so
-        fewer than topn pairs may come back; topn=None returns the NaN scores."""
+        fewer than topn pairs may come back; topn=None returns the NaN scores.
+        indexer (gensim's argument; an index from build_index): only the lists the index probes are searched --
+        the same scores, the nearest rows among those lists; not with restrict_vocab or topn=None."""
+        if indexer is not None:
+            self._check_indexer(topn, restrict_vocab)
         if topn is not None and topn < 1:
             return []
         query, own = self._query(positive, negative)
@@ -264,19 +286,24 @@ class KeyedVectors:
         q = torch.from_numpy(query).to(X.device)
         if topn is None:
             return similarity.scores(X, queries=q, restrict=restrict_vocab, inv_norm=self._inv_norm)[0].cpu().numpy()
-        rows, scores = similarity.knn(X, int(topn) + len(own), queries=q, restrict=restrict_vocab,
-                                      inv_norm=self._inv_norm)
+        if indexer is not None:
+            from node2vec_amd import ann
+
+            rows, scores = ann.search(X, indexer, int(topn) + len(own), queries=q, inv_norm=self._inv_norm)
+        else:
+            rows, scores = similarity.knn(X, int(topn) + len(own), queries=q, restrict=restrict_vocab,
+                                          inv_norm=self._inv_norm)
         rows, scores = rows[0].cpu().numpy(), scores[0].cpu().numpy()
         own = set(own)
         out = [(self.index2word[int(r)], float(s)) for r, s in zip(rows, scores) if r >= 0 and int(r) not in own]
         return out[:int(topn)]
 
-    def similar_by_word(self, word, topn: Optional[int] = 10, restrict_vocab: Optional[int] = None):
-        return self.most_similar(positive=[word], topn=topn, restrict_vocab=restrict_vocab)
+    def similar_by_word(self, word, topn: Optional[int] = 10, restrict_vocab: Optional[int] = None, indexer=None):
+        return self.most_similar(positive=[word], topn=topn, restrict_vocab=restrict_vocab, indexer=indexer)
 
-    def similar_by_vector(self, vector, topn: Optional[int] = 10, restrict_vocab: Optional[int] = None):
+    def similar_by_vector(self, vector, topn: Optional[int] = 10, restrict_vocab: Optional[int] = None, indexer=None):
         return self.most_similar(positive=[np.asarray(vector, dtype=np.float32)], topn=topn,
-                                 restrict_vocab=restrict_vocab)
+                                 restrict_vocab=restrict_vocab, indexer=indexer)
 
     def similarity(self, w1, w2) -> float:
         """cosine of two tokens (gensim: dot(unitvec(wv[w1]), unitvec(wv[w2])))"""
@@ -284,12 +311,21 @@ class KeyedVectors:
         na, nb = np.float32(np.sqrt(np.dot(a, a))), np.float32(np.sqrt(np.dot(b, b)))
         return float(np.dot(a / na if na > 0 else a, b / nb if nb > 0 else b))
 
-    def nearest(self, rows, topn: int = 10, exclude_self: bool = True, restrict_vocab: Optional[int] = None):
+    def nearest(self, rows, topn: int = 10, exclude_self: bool = True, restrict_vocab: Optional[int] = None,
+                indexer=None):
         """The batched form: for every row number in `rows`, its topn nearest rows -- device tensors
-        (rows int64 [len(rows), topn], cosines fp32), best first, a query's own row left out."""
+        (rows int64 [len(rows), topn], cosines fp32), best first, a query's own row left out.  indexer (an index
+        from build_index): the nearest among the lists the index probes; not with restrict_vocab."""
         from node2vec_amd import similarity
 
+        if indexer is not None:
+            self._check_indexer(topn, restrict_vocab)
         self.init_sims()
+        if indexer is not None:
+            from node2vec_amd import ann
+
+            return ann.search(self._device_vectors(), indexer, topn, rows=rows, inv_norm=self._inv_norm,
+                              exclude_self=exclude_self)
         return similarity.knn(self._device_vectors(), topn, rows=rows, restrict=restrict_vocab,
                               inv_norm=self._inv_norm, exclude_self=exclude_self)
 
@@ -757,12 +793,13 @@ class Node2VecHIP(Node2VecBase, _PairQueries, _ClusterQueries, _LabelQueries, _P
             vertex_id = str(vertex_id)
         return list(self.model.wv[vertex_id])  # type: ignore
 
-    def most_similar(self, vertex_id: Union[str, int], topn: int = 10) -> pd.DataFrame:
+    def most_similar(self, vertex_id: Union[str, int], topn: int = 10, indexer=None) -> pd.DataFrame:
         """The topn vertices nearest to vertex_id by cosine of their vectors (model.wv.most_similar):
-        a DataFrame ["id" | "name", "similarity"], names mapped through name_id as in embedding()."""
+        a DataFrame ["id" | "name", "similarity"], names mapped through name_id as in embedding().
+        indexer: an index from model.wv.build_index() for an approximate search."""
         if self.model is None:
             raise ValueError("Model is not available. Please run fit()")
-        hits = self.model.wv.most_similar(str(vertex_id), topn=topn)
+        hits = self.model.wv.most_similar(str(vertex_id), topn=topn, indexer=indexer)
         ids = np.array([int(t) for t, _ in hits], dtype=np.int64)
         sims = np.array([s for _, s in hits], dtype=np.float64)
         if self.name_id is None:
