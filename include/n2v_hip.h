@@ -1053,6 +1053,34 @@ int n2v_ivf_topk(const float *X, const float *inv_norm, int64_t n, int32_t dim, 
                  int64_t *out_rows, float *out_scores, uint32_t *status, void *workspace, int64_t workspace_bytes,
                  void *stream);
 
+/* Silhouette coefficients of a clustering of trained vectors (csrc/n2v_silhouette.hip, DESIGN.md "Cluster
+ * quality").  ADDITIONS ONLY: N2V_ABI_VERSION stays 15.  X, inv_norm, labels, k and metric as for n2v_kmeans_*
+ * (metric: N2V_KMEANS_EUCLIDEAN, the true distance sqrt(max(|x_i|^2 + |x_j|^2 - 2 dot, 0)), or N2V_KMEANS_COSINE,
+ * 1 - dot * inv_norm[i] * inv_norm[j]).  A row whose label is outside [0, k) belongs to no cluster: it is never
+ * counted and never an index.  rows: int64 [m], the rows to score (any order, repeats allowed), or NULL for every
+ * row (then m == n); 0 <= m < 2^31.  For scored row i of label L, n_c rows of label c and S(i, c) = the sum of
+ * d(i, j) over the rows j != i of label c: a = S(i, L) / (n_L - 1); b = the smallest S(i, c) / n_c over c != L with
+ * n_c > 0 (ties: the lowest c; NaN never wins), nearest = that c, or -1 and b = +inf when there is none;
+ * s = (b - a) / max(a, b), and 0 when n_L == 1, nearest == -1 or max(a, b) == 0.  A scored row of no cluster, or
+ * an entry of rows outside [0, n) (never dereferenced), gets a = b = s = NaN and nearest = -1.  a_out, b_out,
+ * s_out: fp64 [m]; nearest_out: int32 [m]; counts_out: int64 [k] (n_c) or NULL.  Distances are fp32, the sums and
+ * all that follows fp64, in one fixed order (no float atomics; written out in csrc/n2v_silhouette.hip and restated
+ * in tests/cpu_silhouette/n2v_silhouette_cpu.c): the result is a function of the arguments alone, bit for bit, and
+ * a row's values do not depend on which other rows are scored with it.  Argument errors are N2V_EINVAL before any
+ * launch: sizes or metric out of range, cosine without inv_norm, rows NULL with m != n, then (n > 0 and m > 0) a
+ * NULL required pointer, a workspace that is NULL, not 16-byte aligned or smaller than
+ * n2v_silhouette_workspace_bytes.  n == 0 or m == 0 is N2V_OK, launches nothing and writes nothing. */
+
+/* Bytes of workspace n2v_silhouette needs (-1 for sizes it refuses, 0 for n == 0 or m == 0): the scored rows padded
+ * to [round_up(m, 64)][round_up(dim, 16)] fp32, fp32 [n] squared norms, the row list int32 [n + 16 k], int32
+ * [ceil(n / slab)][k] counts with slab = round_up(max(1, ceil(n / 2048)), 1024), int32 [k] and int64 [k + 1] (each
+ * part rounded up to 256 bytes). */
+int64_t n2v_silhouette_workspace_bytes(int64_t n, int32_t dim, int32_t k, int64_t m);
+int n2v_silhouette(const float *X, const float *inv_norm, int64_t n, int32_t dim, const int32_t *labels, int32_t k,
+                   int32_t metric, const int64_t *rows, int64_t m, double *a_out, double *b_out, double *s_out,
+                   int32_t *nearest_out, int64_t *counts_out, void *workspace, int64_t workspace_bytes,
+                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,10 @@ order of fp32 / fp64 operations (DESIGN.md "Clustering"): the same call gives th
 A cluster that loses all its rows keeps its centroid (scikit-learn relocates it).  A row whose distances are all
 NaN gets label -1, joins no cluster and is counted in n_unassigned.
 
+silhouette_samples / silhouette_score (csrc/n2v_silhouette.hip; DESIGN.md "Cluster quality") say how good a
+clustering is, which inertia cannot: every distance of a scored row to every other row, on the GPU, in one fixed
+order as well.
+
 Device tensors in and out.  There is no CPU path: a missing GPU or library raises.
 """
 from typing import NamedTuple, Optional, Tuple
@@ -32,6 +36,14 @@ class KMeansResult(NamedTuple):
     n_iter: int
     converged: bool
     n_unassigned: int
+
+
+class SilhouetteResult(NamedTuple):
+    s: torch.Tensor        # fp64 [m]: (b - a) / max(a, b); NaN for a row of no cluster
+    a: torch.Tensor        # fp64 [m]: mean distance to the other rows of the row's cluster
+    b: torch.Tensor        # fp64 [m]: the smallest mean distance to the rows of another cluster
+    nearest: torch.Tensor  # int32 [m]: that cluster, -1: none
+    counts: torch.Tensor   # int64 [k]: rows per cluster
 
 
 def check_metric(metric: str) -> None:
@@ -241,3 +253,90 @@ def kmeans(X: torch.Tensor, k: int, metric: str = "euclidean", init="k-means++",
             if best is None or res.inertia < best.inertia:
                 best = res
     return best
+
+
+def _labels(labels, n: int, k: Optional[int]) -> Tuple[torch.Tensor, int]:
+    """(labels int32 [n] where they are, k): checked on the host side of the call, before anything needs a device"""
+    if isinstance(labels, KMeansResult):
+        k = labels.centroids.shape[0] if k is None else k
+        labels = labels.labels
+    if not isinstance(labels, torch.Tensor) or labels.ndim != 1 or labels.shape[0] != n:
+        raise ValueError(f"labels must be a [{n}] tensor")
+    if labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool:
+        raise ValueError(f"labels must be integers, not {labels.dtype}")
+    # MAX_K is a label of no cluster whatever k is: nothing wraps on the way to int32
+    labels = labels.to(torch.int64).clamp(min=-1, max=MAX_K).to(torch.int32)
+    if k is None:
+        k = max(int(labels.max()) + 1, 1) if n else 1
+    return labels, check_k(k)
+
+
+def sample_rows(labels: torch.Tensor, k: int, sample_size: Optional[int], seed: int = 0) -> Optional[torch.Tensor]:
+    """silhouette_score's sample: sample_size of the rows whose label is in [0, k), without replacement, from
+    numpy.random.default_rng(seed), ascending (int64, on the host); None when every such row is taken"""
+    if sample_size is None:
+        return None
+    if int(sample_size) < 1:
+        raise ValueError("sample_size must be >= 1")
+    have = torch.nonzero((labels >= 0) & (labels < k))[:, 0].cpu().numpy()
+    if int(sample_size) >= len(have):
+        return None
+    rng = np.random.default_rng(seed)
+    return torch.from_numpy(np.sort(have[rng.choice(len(have), size=int(sample_size), replace=False)]))
+
+
+def silhouette_samples(X: torch.Tensor, labels, metric: str = "euclidean", k: Optional[int] = None, rows=None,
+                       inv_norm: Optional[torch.Tensor] = None) -> SilhouetteResult:
+    """The silhouette of rows of X under a clustering (csrc/n2v_silhouette.hip): for row i of label L,
+    a = the mean distance to the other rows of cluster L, b = the smallest mean distance to the rows of another
+    non-empty cluster (ties: the lowest cluster), nearest = that cluster, s = (b - a) / max(a, b); s = 0 for a
+    cluster of one row, for a = b = 0 and when no other cluster has rows.  The distance is the true Euclidean
+    distance (scikit-learn's default; not the squared one kmeans reports) or 1 - cosine.  labels: int [n] or a
+    KMeansResult; a label outside [0, k) is no cluster: the row is never counted, and scores NaN when asked for.
+    k: clusters, labels.max() + 1 when not given.  rows: the rows to score (any order, repeats allowed), every row
+    when not given; each is scored against ALL rows, so its values are the same bits whichever rows come with it.
+    Every distance is computed: 2 m n dim FLOPs, nothing of size m x n stored.  Device tensors out."""
+    check_metric(metric)
+    n, dim = _dense.shape(X)
+    labels, k = _labels(labels, n, k)
+    if rows is not None:
+        rows = torch.as_tensor(rows)
+        if rows.ndim != 1 or rows.dtype.is_floating_point or rows.dtype.is_complex or rows.dtype == torch.bool:
+            raise ValueError("rows must be a 1-D tensor of row numbers")
+    X = _dense.matrix(X)
+    labels = labels.to(X.device).contiguous()
+    norms = _norms(X, metric, inv_norm)
+    if rows is not None:
+        rows = rows.to(device=X.device, dtype=torch.int64).contiguous()
+    m = n if rows is None else int(rows.shape[0])
+    a = torch.empty(m, dtype=torch.float64, device=X.device)
+    b = torch.empty(m, dtype=torch.float64, device=X.device)
+    s = torch.empty(m, dtype=torch.float64, device=X.device)
+    nearest = torch.empty(m, dtype=torch.int32, device=X.device)
+    counts = torch.zeros(k, dtype=torch.int64, device=X.device)
+    with torch.cuda.device(X.device):
+        ws = _dense.workspace(_lib.load().n2v_silhouette_workspace_bytes, n, dim, k, m, device=X.device)
+        _lib.check(_lib.load().n2v_silhouette(X.data_ptr(), _dense.ptr(norms), n, dim, labels.data_ptr(), k,
+                                              METRICS[metric], _dense.ptr(rows), m, a.data_ptr(), b.data_ptr(),
+                                              s.data_ptr(), nearest.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                              ws.numel(), _lib.current_stream_ptr()), "n2v_silhouette")
+    return SilhouetteResult(s, a, b, nearest, counts)
+
+
+def silhouette_score(X: torch.Tensor, labels, metric: str = "euclidean", sample_size: Optional[int] = None,
+                     seed: int = 0, k: Optional[int] = None, inv_norm: Optional[torch.Tensor] = None) -> float:
+    """The mean silhouette (float64) over the rows that have a cluster.  sample_size: that many of those rows
+    (sample_rows: without replacement, from numpy.random.default_rng(seed); all of them when there are no more),
+    each scored against every row -- a sampled value is the row's exact silhouette and the cost is
+    sample_size * n distances (scikit-learn scores its sample against the sample alone).  Fewer than two
+    clusters with rows is a ValueError."""
+    check_metric(metric)
+    n, _ = _dense.shape(X)
+    labels, k = _labels(labels, n, k)
+    member = (labels >= 0) & (labels < k)
+    if int(torch.bincount(labels[member].long(), minlength=k).count_nonzero()) < 2:
+        raise ValueError("the silhouette needs at least two clusters with rows")
+    rows = sample_rows(labels, k, sample_size, seed)
+    res = silhouette_samples(X, labels, metric, k, rows, inv_norm)
+    s = res.s if rows is not None else res.s[member.to(res.s.device)]
+    return float(s.mean())

@@ -389,6 +389,22 @@ class KeyedVectors:
             inv_norm = self._inv_norm[:n]
         return cluster.kmeans(X, k, metric=metric, inv_norm=inv_norm, **kw)
 
+    def silhouette(self, labels_or_result, metric: str = "cosine", restrict_vocab: Optional[int] = None, **kw):
+        """the silhouette of every vector under a clustering, on the GPU (node2vec_amd.cluster.silhouette_samples,
+        whose other arguments pass through): a SilhouetteResult.  labels_or_result: a label tensor (one per row,
+        or per row of restrict_vocab) or a KMeansResult.  The default metric is cosine over the cached init_sims
+        norms, as for kmeans: score a clustering by the metric it was made with."""
+        from node2vec_amd import cluster
+
+        cluster.check_metric(metric)
+        n = self._first_rows(restrict_vocab)
+        inv_norm = None
+        if metric == "cosine":
+            self.init_sims()
+            inv_norm = self._inv_norm[:n]
+        return cluster.silhouette_samples(self._device_vectors()[:n], labels_or_result, metric=metric,
+                                          inv_norm=inv_norm, **kw)
+
     def logreg(self, Y, restrict_vocab: Optional[int] = None, **kw):
         """one-vs-rest logistic regression of the vectors on the GPU (node2vec_amd.classify.fit, whose other
         arguments pass through): a LogRegResult; row i of Y (bool or 0/1 [n, c]) holds the labels of token
@@ -530,6 +546,8 @@ class _ClusterQueries:
     name_id = None
     clusters = None
     kmeans_result = None
+    silhouette_score = None
+    _cluster_metric = "cosine"
 
     def cluster(self, k: int, metric: str = "cosine", **kw) -> pd.DataFrame:
         """["id" | "name", "cluster"]: the k-means cluster of every vocabulary vertex, in vocabulary order
@@ -553,7 +571,21 @@ class _ClusterQueries:
             self.clusters = pd.DataFrame({"id": ids, "cluster": labels})
         else:
             self.clusters = pd.DataFrame({"name": names.reindex(ids).to_numpy(), "cluster": labels})
+        self._cluster_metric = metric
         return self.clusters
+
+    def silhouette(self) -> pd.DataFrame:
+        """self.clusters plus a "silhouette" column: how well every vertex sits in the cluster cluster() gave it
+        (model.wv.silhouette of self.kmeans_result, by the metric it was clustered with; NaN for a vertex of no
+        cluster).  The mean over the clustered vertices is kept as self.silhouette_score.  cluster() first."""
+        if self.model is None or self.kmeans_result is None:
+            raise ValueError("Model is not available. Please run fit()" if self.model is None else
+                             "Clusters are not available. Please run cluster()")
+        res = self.model.wv.silhouette(self.kmeans_result, metric=self._cluster_metric,
+                                       restrict_vocab=len(self.clusters))
+        member = self.kmeans_result.labels >= 0
+        self.silhouette_score = float(res.s[member.to(res.s.device)].mean())
+        return self.clusters.assign(silhouette=res.s.cpu().numpy())
 
 
 class _LabelQueries:
