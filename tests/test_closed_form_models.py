@@ -1,7 +1,8 @@
 """The closed forms of csrc/n2v_unit_core.h were derived and first checked as Python models
 (scripts/models/): exact integer bucket arithmetic against the pairing loop of
 generate_alias_tables (reference randomwalk.py:175-189) on random rows of the three class values.
-The HIP code itself is compared with the oracle in the -m gpu tests; this keeps the models (the
+The HIP code itself is compared with the oracle in the -m gpu tests -- the dyadic forms row by row in
+test_closed_form_rows_gpu.py, the forms with margins in test_margin_adversary_gpu.py; this keeps the models (the
 derivation DESIGN.md cites) running: no mismatch on a few thousand random rows each."""
 import os
 import subprocess
