@@ -1081,6 +1081,41 @@ int n2v_silhouette(const float *X, const float *inv_norm, int64_t n, int32_t dim
                    int32_t *nearest_out, int64_t *counts_out, void *workspace, int64_t workspace_bytes,
                    void *stream);
 
+/* Exact t-SNE of 2-D points (csrc/n2v_tsne.hip, DESIGN.md "t-SNE").  ADDITIONS ONLY: N2V_ABI_VERSION stays 15.
+ * Y: row-major fp32 [n, 2], 8-byte aligned, 0 <= n < 2^31.  A pair (i, j) in fp32, one rounding per operation:
+ * dx = yi.x - yj.x; dy = yi.y - yj.y; d2 = fmaf(dy, dy, dx * dx); w = 1.0f / (1.0f + d2), correctly rounded.
+ * Every result is a function of the arguments alone, bit for bit (no float atomics; the orders below are restated
+ * in tests/cpu_tsne/n2v_tsne_cpu.c).  Argument errors are N2V_EINVAL before any launch: n out of range, then
+ * (n > 0) a NULL or misaligned pointer, a workspace that is NULL, not 16-byte aligned or smaller than
+ * n2v_tsne_workspace_bytes, Y_next == Y.  n == 0 is N2V_OK, launches nothing and writes nothing. */
+
+/* The fixed order of the repulsion as numbers, a pure function of n: columns are cut into tiles of *tile (1024)
+ * and into *n_slabs slabs of *slab_cols columns (whole tiles; n_slabs * slab_cols >= n), so that
+ * ceil(n / 256) * n_slabs is about 2048 blocks at most. */
+int n2v_tsne_plan(int64_t n, int32_t *tile, int64_t *slab_cols, int32_t *n_slabs);
+/* Bytes of workspace n2v_tsne_repulse needs (-1 for an n it refuses, 0 for n == 0): fp64 [n_slabs][n][3] partials,
+ * fp64 [ceil(n / 256)] block sums and a ticket (each part rounded up to 256 bytes). */
+int64_t n2v_tsne_workspace_bytes(int64_t n);
+/* rep_out fp64 [n, 2]: rep_i = sum_{j != i} w_ij^2 (y_i - y_j); zrow_out fp64 [n]: sum_{j != i} w_ij; z_out fp64
+ * [1]: their sum.  j == i is skipped by index.  Order: per (row, slab) and tile, j ascending from +0 in fp32:
+ * sw = sw + w; w2 = w * w; sx = fmaf(w2, dx, sx); sy = fmaf(w2, dy, sy); at the tile's end the three sums are added
+ * (as doubles) to the slab's fp64 partials, tiles ascending from 0.0; the slabs' partials are added ascending from
+ * 0.0.  z = 0.0 + b_0 + b_1 + .., b_k = 0.0 + zrow[256 k] + zrow[256 k + 1] + .. (at most 256 rows), all fp64. */
+int n2v_tsne_repulse(const float *Y, int64_t n, double *rep_out, double *zrow_out, double *z_out, void *workspace,
+                     int64_t workspace_bytes, void *stream);
+/* One iteration's attraction, gradient and update in one launch.  P as CSR: rowptr int64 [n + 1], col int32 [nnz],
+ * val fp32 [nnz] (a row's range is clamped to [0, nnz); a column outside [0, n) contributes nothing).  rep, Z:
+ * n2v_tsne_repulse's of the same Y.  Row i: lane l of 16 takes entries rowptr[i] + l, + 16, .. ascending, a = val *
+ * w; ax = fmaf(a, dx, ax); ay likewise, from +0; the 16 sums fold by v[l] = v[l] + v[l ^ m], m = 8, 4, 2, 1.  Per
+ * coordinate: r = (float)(rep / Z[0]); g = 4.0f * (exaggeration * a - r); gain = ((g > 0) != (vel > 0)) ? gain +
+ * 0.2f : gain * 0.8f; gain = fmaxf(gain, min_gain); vel = momentum * vel - learning_rate * (gain * g); y_next = y +
+ * vel -- every product, sum and difference rounded once.  vel, gain: fp32 [n, 2], updated in place; Y_next, grad_out:
+ * fp32 [n, 2], Y_next a buffer other than Y (other rows still read Y). */
+int n2v_tsne_step(const int64_t *rowptr, const int32_t *col, const float *val, int64_t nnz, const float *Y,
+                  const double *rep, const double *Z, int64_t n, float exaggeration, float learning_rate,
+                  float momentum, float min_gain, float *vel, float *gain, float *Y_next, float *grad_out,
+                  void *stream);
+
 #ifdef __cplusplus
 }
 #endif

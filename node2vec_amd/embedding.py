@@ -464,6 +464,17 @@ class KeyedVectors:
             inv_norm = self._inv_norm[:n]
         return pca.transform(self._device_vectors()[:n], result, inv_norm=inv_norm)
 
+    def tsne(self, perplexity: float = 30.0, restrict_vocab: Optional[int] = None, **kw):
+        """the t-SNE map of the vectors on the GPU (node2vec_amd.tsne.fit, whose other arguments pass through): a
+        TSNEResult whose embedding[i] is the 2-D point of token index2word[i].  The neighbours are cosine over the
+        cached init_sims norms.  The exact gradient costs O(n^2) per iteration: restrict_vocab fits only the first
+        rows."""
+        from node2vec_amd import tsne
+
+        n = self._first_rows(restrict_vocab)
+        self.init_sims()
+        return tsne.fit(self._device_vectors()[:n], perplexity=perplexity, inv_norm=self._inv_norm[:n], **kw)
+
     @classmethod
     def load_word2vec_format(cls, fname: str) -> "KeyedVectors":
         with open(fname) as f:
@@ -657,6 +668,28 @@ class _ProjectQueries:
         coords = wv.project(self.pca_result).cpu().numpy()
         who = {"id": ids} if names is None else {"name": names.reindex(ids).to_numpy()}
         return pd.DataFrame({**who, **{f"x{j}": coords[:, j] for j in range(coords.shape[1])}})
+
+    tsne_result = None
+
+    def tsne(self, **kw) -> pd.DataFrame:
+        """["id" | "name", "x0", "x1"]: every vocabulary vertex on the t-SNE map of the vectors, in vocabulary order
+        (model.wv.tsne, whose arguments pass through).  Names go through name_id as in project().  The TSNEResult
+        is kept as self.tsne_result."""
+        if self.model is None:
+            raise ValueError("Model is not available. Please run fit()")
+        wv = self.model.wv
+        ids = wv.ids if wv.ids is not None else np.array([int(t) for t in wv.index2word], dtype=np.int64)
+        names = None
+        if self.name_id is not None:
+            names = self.name_id.drop_duplicates("id", keep="last").set_index("id")["name"]
+            missing = ~pd.Index(ids).isin(names.index)
+            if missing.any():
+                raise KeyError(int(ids[missing][0]))
+        self.tsne_result = wv.tsne(**kw)
+        coords = self.tsne_result.embedding.cpu().numpy()
+        ids = ids[:coords.shape[0]]  # restrict_vocab
+        who = {"id": ids} if names is None else {"name": names.reindex(ids).to_numpy()}
+        return pd.DataFrame({**who, "x0": coords[:, 0], "x1": coords[:, 1]})
 
 
 class Node2VecHIP(Node2VecBase, _PairQueries, _ClusterQueries, _LabelQueries, _ProjectQueries):
