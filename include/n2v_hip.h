@@ -108,8 +108,8 @@ typedef struct n2v_graph {
                                    T >= 2 (mixed; 65536 in production): the lists of the edges INTO a row
                                    of T entries or more are uint32 and lie behind the uint16 lists of all
                                    other edges -- see n2v_wedge_build */
-  int32_t reserved;             /* 0 (diagnostics: bit 0 set = do not use the all-tables kernel,
-                                   bit 1 set = do not use wedge_slots) */
+  int32_t reserved;             /* 0 (diagnostics: N2V_DIAG_NO_TABLES_KERNEL = do not use the all-tables kernel,
+                                   N2V_DIAG_NO_SLOTS_KERNEL = do not use wedge_slots) */
   const uint64_t *hops8;        /* the 8-byte hop table (n2v_hops8_build) or NULL */
   int32_t hop8_col_bits;        /* field widths of a hops8 entry, see n2v_hops8_build */
   int32_t hop8_row_bits;
@@ -177,6 +177,10 @@ typedef struct n2v_graph {
 /* bit 1 of reserved2 (ABI 15): the wedge slots of the edges into rows of wedge_wide .. wedge_wide + 65536 entries are
  * FOLDED slots (n2v_wedge_slots_fold) -- the exact slots kernel then steps those rows like every other */
 #define N2V_SLOTS_FOLDED 2
+/* the diagnostic bits of `reserved`: an exact biased walk on a unit-weight graph that carries every per-edge table
+ * keeps the tables but walks with another kernel (same walks, bit for bit) */
+#define N2V_DIAG_NO_TABLES_KERNEL 1 /* bit 0: not the all-tables kernels (a lane per walker, no step needs the wave) */
+#define N2V_DIAG_NO_SLOTS_KERNEL 2  /* bit 1: not the one of them that reads wedge_slots */
 
 int n2v_abi_version(void);
 const char *n2v_status_string(int code);

@@ -15,6 +15,7 @@ ABI_VERSION = 15
 OK, EINVAL, ELAUNCH, ENOGPU = 0, -1, -2, -3
 ST_ZERODIV, ST_RANGE, ST_OVERFLOW = 1, 2, 4
 WALK_EXACT, WALK_FAST = 0, 1
+DIAG_NO_TABLES_KERNEL, DIAG_NO_SLOTS_KERNEL = 1, 2  # bits of n2v_graph.reserved
 WIRE_F32, WIRE_BF16 = 0, 1
 PAIR_DOT, PAIR_COSINE = 0, 1
 PAIR_AVERAGE, PAIR_HADAMARD, PAIR_L1, PAIR_L2 = 0, 1, 2, 3

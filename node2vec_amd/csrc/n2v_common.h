@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/n2v_hip.h"
 
 #define N2V_HIP_CHECK(expr)                         \
@@ -27,6 +29,18 @@ inline int64_t resident_blocks(const void *kernel, int block_threads, size_t dyn
       occ > 0)
     per_cu = occ;
   return (int64_t)cus * per_cu;
+}
+
+// One launch of a persistent kernel: the `blocks` the work asks for, at most kCapMult x those resident at once, and
+// the launch's error.  One typed pointer serves the occupancy query and the launch, so the instance asked about is
+// the instance launched; `args` are the kernel's arguments, converted to its parameter types.
+template <int kCapMult = 1, typename... KArgs>
+inline hipError_t launch_resident(void (*kernel)(KArgs...), int block_threads, size_t dyn_lds, int64_t blocks,
+                                  hipStream_t stream, std::common_type_t<KArgs>... args) {
+  const int64_t cap = kCapMult * resident_blocks((const void *)kernel, block_threads, dyn_lds);
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3((unsigned)block_threads), dyn_lds, stream, args...);
+  return hipGetLastError();
 }
 
 // Work distribution of a short single-step launch (n2v_partition_step): k items, a few per wave.

@@ -1,13 +1,7 @@
 // n2v_partition.hip -- the entry points of graph-partitioned walking (node2vec_amd/partitioned.py,
 // SURVEY.md 8f-4): the reference's per-step joins (fugue.py:146-149) for a graph whose rows are
 // split over ranks by vertex range.
-//   n2v_partition_step   one step of the walkers resident on one part.  Dispatches to
-//                          - partition_step_wedge_kernel (n2v_walk_wedge.hip): unit weights, the
-//                            wedge list of the edge walked last travelled with the walker (or
-//                            p == q == 1): one LANE per walker, closed-form pairing;
-//                          - partition_step_unit_kernel (n2v_walk_unit.hip): unit weights, the row
-//                            of the previous vertex travelled: one wave per walker;
-//                          - partition_step_kernel (n2v_walk.hip): any weights, one wave per walker.
+//   (n2v_partition_step, one step of the walkers resident on one part, is dispatched in n2v_capi.hip)
 //   n2v_partition_route  what happens to every walker after its step: path record, next header,
 //                        destination, words to carry (elementwise)
 //   n2v_partition_group  the walkers grouped by destination: a stable counting sort (per-block
@@ -17,49 +11,6 @@
 //                        host: every walker is appended to the mailbox of its destination
 //                        (wave-aggregated atomics), its wedge list copied behind it
 #include "n2v_common.h"
-
-extern "C" int n2v_partition_step_generic_launch(const int64_t *rowptr, const int32_t *col,
-                                                 const float *w, const double *w64, int64_t lo,
-                                                 int64_t n_local, const int64_t *head,
-                                                 int32_t head_cols, const int64_t *src_ptr,
-                                                 const int32_t *src_ids, int64_t k, double p,
-                                                 double q, uint64_t seed, int32_t *next_out,
-                                                 int64_t *edge_out, uint32_t *status,
-                                                 void *stream);  // n2v_walk.hip
-extern "C" int n2v_partition_step_unit_try(const int64_t *rowptr, const int32_t *col, int64_t lo,
-                                           int64_t n_local, const int64_t *head, int32_t head_cols,
-                                           const int64_t *src_ptr, const int32_t *src_ids,
-                                           int32_t wedge_lists, int64_t k, double p, double q,
-                                           uint64_t seed, int32_t *next_out, int64_t *edge_out,
-                                           uint32_t *status, void *stream);  // n2v_walk_unit.hip
-
-extern "C" int n2v_partition_step(const int64_t *rowptr, const int32_t *col, const float *w,
-                                  const double *w64, int64_t lo, int64_t n_local,
-                                  const int64_t *head, int32_t head_cols, const int64_t *src_ptr,
-                                  const int32_t *src_ids, int32_t src_kind, int64_t k, double p,
-                                  double q, uint64_t seed, int32_t *next_out, int64_t *edge_out,
-                                  uint32_t *status, void *stream) {
-  if (k < 0 || n_local < 0 || k >= 0xfffffff0ll || (w && w64)) return N2V_EINVAL;
-  if (p == 0.0 || q == 0.0) return N2V_EINVAL;  // randomwalk.py:209-212 (ValueError upstream)
-  if (src_kind != N2V_SRC_ROWS && src_kind != N2V_SRC_WEDGES && src_kind != N2V_SRC_WEDGES_AT)
-    return N2V_EINVAL;
-  if (head_cols < 4) return N2V_EINVAL;  // (wedge lists with p or q != 1: 5, checked below)
-  if (src_kind != N2V_SRC_ROWS && (w || w64)) return N2V_EINVAL;  // unit-weight parts only
-  if (k == 0) return N2V_OK;
-  if (!rowptr || !head || !next_out || !status) return N2V_EINVAL;  // (col: NULL for a part without edges)
-  if (q != 1.0 && !src_ptr) return N2V_EINVAL;
-  if (hipMemsetAsync(status + 1, 0, sizeof(uint32_t), (hipStream_t)stream) != hipSuccess)
-    return N2V_ELAUNCH;
-  if (!w && !w64) {  // unit weights: the closed forms of n2v_walk_unit.hip
-    const int rc = n2v_partition_step_unit_try(rowptr, col, lo, n_local, head, head_cols, src_ptr,
-                                               src_ids, src_kind == N2V_SRC_ROWS ? 0 : src_kind, k, p,
-                                               q, seed, next_out, edge_out, status, stream);
-    if (rc != 0) return rc < 0 ? rc : N2V_OK;
-  }
-  if (src_kind != N2V_SRC_ROWS) return N2V_EINVAL;  // (p, q) outside the unit kernels' range
-  return n2v_partition_step_generic_launch(rowptr, col, w, w64, lo, n_local, head, head_cols, src_ptr,
-                                           src_ids, k, p, q, seed, next_out, edge_out, status, stream);
-}
 
 namespace n2v {
 

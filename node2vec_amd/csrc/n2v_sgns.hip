@@ -466,13 +466,6 @@ extern "C" int n2v_cum_index_build(const uint32_t *cum_table, int64_t n_vocab, i
   return N2V_OK;
 }
 
-// the opt-in batched variant (n2v_sgns_batched.hip)
-extern "C" int n2v_sgns_batched_launch(const int32_t *walks, int64_t n_walks, int32_t walk_len,
-                                       float *syn0, float *syn1neg, const uint32_t *cum_table,
-                                       const uint32_t *sample_int, const float *exp_table,
-                                       const n2v_sgns_params *P, unsigned long long *pairs_out,
-                                       void *stream, int64_t *dry_waves);
-
 // the instance with a window cache of `ring` rows (0: none)
 template <int VEC, typename Launch>
 static int launch_ring(int ring, Launch launch) {
@@ -494,8 +487,8 @@ static int sgns_train_impl(const int32_t *walks, int64_t n_walks, int32_t walk_l
   if (dry_waves) *dry_waves = 0;
   if (n_walks == 0) return N2V_OK;
   if (P->batched)
-    return n2v_sgns_batched_launch(walks, n_walks, walk_len, syn0, syn1neg, cum_table,
-                                   sample_int, exp_table, P, pairs_out, stream, dry_waves);
+    return n2v::launch_sgns_batched(walks, n_walks, walk_len, syn0, syn1neg, cum_table,
+                                    sample_int, exp_table, P, pairs_out, stream, dry_waves);
   using namespace n2v;
   const int V = vec_of(P->dim);
   // the window cache (kRing): rows of 64 * V floats, 2 * window + 2 of them (12 or 16), when the

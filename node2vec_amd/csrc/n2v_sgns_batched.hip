@@ -595,14 +595,9 @@ static int launch_tiles(int trows, int kc, Launch launch) {
   return kc == 3 ? launch(sgns_batched_kernel<VEC, 16, 3>) : launch(sgns_batched_kernel<VEC, 16, 4>);
 }
 
-}  // namespace n2v
-
-extern "C" int n2v_sgns_batched_launch(const int32_t *walks, int64_t n_walks, int32_t walk_len,
-                                       float *syn0, float *syn1neg, const uint32_t *cum_table,
-                                       const uint32_t *sample_int, const float *exp_table,
-                                       const n2v_sgns_params *P, unsigned long long *pairs_out,
-                                       void *stream, int64_t *dry_waves) {
-  using namespace n2v;
+int launch_sgns_batched(const int32_t *walks, int64_t n_walks, int32_t walk_len, float *syn0, float *syn1neg,
+                        const uint32_t *cum_table, const uint32_t *sample_int, const float *exp_table,
+                        const n2v_sgns_params *P, unsigned long long *pairs_out, void *stream, int64_t *dry_waves) {
   // what the tiles hold: dim 64 / 128 / 256 (64 lanes x 1 / 2 / 4 floats), <= 15 window
   // positions + 1 in the ring (window <= 7), <= 16 target rows (negative <= 15)
   if (P->dim != 64 && P->dim != 128 && P->dim != 256) return N2V_EINVAL;
@@ -634,3 +629,5 @@ extern "C" int n2v_sgns_batched_launch(const int32_t *walks, int64_t n_walks, in
     default: return launch_tiles<4>(trows, kc, launch);
   }
 }
+
+}  // namespace n2v

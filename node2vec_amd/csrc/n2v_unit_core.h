@@ -9,7 +9,7 @@
 //   lane_case_a       any row whose only underfull class is "other": O(return + shared) steps
 //   lane_pairing_list any row, any arrangement: O(n), classes read off the list on the way
 #pragma once
-#include "n2v_common.h"
+#include "n2v_walk_host.h"  // UnitConsts
 
 namespace n2v {
 
@@ -23,14 +23,6 @@ __device__ __forceinline__ T pick3(bool first, bool second, T a, T b, T c) {
 // decline on such a row is a TIE of the exact process (codes 3, 5, 15, 20) -- the reference's rounding decides it and only a
 // replay knows.
 #define N2V_DECLINE(code) return -1
-
-struct UnitConsts {
-  double bR, bM, bO;     // 1/p, 1, 1/q
-  int64_t TR, TM, TO;    // the same times 2^20 (exact integers; dyadic kernel only)
-  int64_t gR, gM, gO;    // TR, TM, TO divided by their greatest common divisor
-  double fR, fM, fO;     // the same as fp64 (exact): the closed forms compute in doubles
-  int dyadic;            // 1/p, 1/q are multiples of 2^-20: TR .. fO are valid
-};
 
 // ---- pieces of the per-lane step from the class counts (n2v_wedge_step.h, n2v_walk_unit.hip) ----------------
 // avg (:172) for dyadic p, q: the row sum is an exact integer combination of the class counts (T* = b * 2^20),
@@ -1281,17 +1273,3 @@ __device__ __forceinline__ int lane_pairing_list(int n, int pick, double r2, dou
 }
 
 }  // namespace n2v
-
-// the kernel of n2v_walk_wedge.hip (hop table + wedge table present): 1 = launched, 0 = does not apply
-int n2v_walk_wedge_try(const n2v_graph *g, const int32_t *start_ids, int64_t n_start,
-                       int32_t num_walks, int32_t walk_length, double p, double q,
-                       const n2v::UnitConsts &K, uint64_t seed, int32_t *walks_out,
-                       uint8_t *valid_out, uint32_t *status, void *stream);
-
-// the wedge-list instance of n2v_partition_step (n2v_walk_wedge.hip): 1 = launched, < 0 on error
-int n2v_partition_step_wedge_launch(const int64_t *rowptr, const int32_t *col, int64_t lo,
-                                    int64_t n_local, const int64_t *head, int32_t head_cols,
-                                    const int64_t *src_ptr, const int32_t *src_ids, int32_t src_at,
-                                    int64_t k, double p, double q, const n2v::UnitConsts &K, uint64_t seed,
-                                    int32_t *next_out, int64_t *edge_out, uint32_t *status,
-                                    void *stream);

@@ -268,4 +268,10 @@ inline int launch_trainer(void (*kernel)(KArgs...), LaunchGeometry g, size_t lds
   return N2V_OK;
 }
 
+// the batched skip-gram trainer (n2v_sgns_batched.hip), checked and launched for n2v_sgns_train (n2v_sgns.hip) when
+// P->batched is set; dry_waves as launch_trainer's
+int launch_sgns_batched(const int32_t *walks, int64_t n_walks, int32_t walk_len, float *syn0, float *syn1neg,
+                        const uint32_t *cum_table, const uint32_t *sample_int, const float *exp_table,
+                        const n2v_sgns_params *P, unsigned long long *pairs_out, void *stream, int64_t *dry_waves);
+
 }  // namespace n2v

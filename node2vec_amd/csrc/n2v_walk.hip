@@ -24,6 +24,7 @@
 //           ballots + v_readlane), with the same fp64 operations in the same
 //           order, and stops as soon as slot `pick` has been paired.
 #include "n2v_alias_core.h"
+#include "n2v_walk_host.h"
 
 namespace n2v {
 
@@ -766,63 +767,35 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 7) void weighted_step_wave_ker
 
 }  // namespace n2v
 
-extern "C" int n2v_walk_exact_launch(const n2v_graph *g, const int32_t *start_ids,
-                                     int64_t n_start, int32_t num_walks, int32_t walk_length,
-                                     double p, double q, uint64_t seed, int32_t *walks_out,
-                                     uint8_t *valid_out, uint32_t *status, void *stream) {
-  const int64_t total = n_start * (int64_t)num_walks;
-  if (total == 0) return N2V_OK;
-  int64_t blocks = (total + n2v::kWavesPerBlock - 1) / n2v::kWavesPerBlock;
-  const int64_t cap = n2v::resident_blocks((const void *)n2v::walk_exact_kernel,
-                                           n2v::kWavesPerBlock * 64, 0);
-  if (blocks > cap) blocks = cap;
-  // status[1] is the kernel's walker counter: start it at zero on the same stream
-  if (hipMemsetAsync(status + 1, 0, sizeof(uint32_t), (hipStream_t)stream) != hipSuccess)
-    return N2V_ELAUNCH;
-  hipLaunchKernelGGL(n2v::walk_exact_kernel, dim3((unsigned)blocks),
-                     dim3(n2v::kWavesPerBlock * 64), 0, (hipStream_t)stream, *g, start_ids,
-                     n_start, num_walks, walk_length, p, q, seed, walks_out, valid_out, status);
-  N2V_HIP_CHECK(hipGetLastError());
-  return N2V_OK;
+namespace n2v {
+
+int launch_walk_exact(const WalkArgs &a) {
+  return launch_status(launch_resident(walk_exact_kernel, kWavesPerBlock * 64, 0,
+                                       (a.total() + kWavesPerBlock - 1) / kWavesPerBlock, a.stream, *a.g, a.start_ids,
+                                       a.n_start, a.num_walks, a.walk_length, a.p, a.q, a.seed, a.walks_out,
+                                       a.valid_out, a.status));
 }
 
-// the generic (any weights) instance of n2v_partition_step (n2v_partition.hip dispatches):
-// status[1] was zeroed by the caller
-extern "C" int n2v_partition_step_generic_launch(const int64_t *rowptr, const int32_t *col,
-                                                 const float *w, const double *w64, int64_t lo,
-                                                 int64_t n_local, const int64_t *head,
-                                                 int32_t head_cols, const int64_t *src_ptr,
-                                                 const int32_t *src_ids, int64_t k, double p,
-                                                 double q, uint64_t seed, int32_t *next_out,
-                                                 int64_t *edge_out, uint32_t *status, void *stream) {
-  int64_t blocks = (k + n2v::kWavesPerBlock - 1) / n2v::kWavesPerBlock;
-  const int64_t cap = n2v::resident_blocks((const void *)n2v::partition_step_kernel,
-                                           n2v::kWavesPerBlock * 64, 0);
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(n2v::partition_step_kernel, dim3((unsigned)blocks),
-                     dim3(n2v::kWavesPerBlock * 64), 0, (hipStream_t)stream, rowptr, col, w, w64,
-                     lo, n_local, head, (int)head_cols, src_ptr, src_ids, k, p, q, seed, next_out,
-                     edge_out, status);
-  N2V_HIP_CHECK(hipGetLastError());
-  return N2V_OK;
+// the generic (any weights) instance of n2v_partition_step
+int launch_step_generic(const StepArgs &a) {
+  return launch_status(launch_resident(partition_step_kernel, kWavesPerBlock * 64, 0,
+                                       (a.k + kWavesPerBlock - 1) / kWavesPerBlock, a.stream, a.rowptr, a.col, a.w,
+                                       a.w64, a.lo, a.n_local, a.head, (int)a.head_cols, a.src_ptr, a.src_ids, a.k,
+                                       a.p, a.q, a.seed, a.next_out, a.edge_out, a.status));
 }
-
 
 // the long rows of n2v_walk_weighted_step (n2v_walk_wlanes.hip): status[1] must be zero at launch
-extern "C" int n2v_weighted_step_wave_launch(const n2v_graph *g, const int32_t *start_ids, int32_t num_walks,
-                                             const int64_t *order, int64_t n_rows, int32_t min_n,
-                                             int32_t step, int32_t walk_length, double p, double q,
-                                             uint64_t seed, int64_t *edge_state, int32_t *walks,
-                                             uint8_t *valid, uint32_t *status, void *stream) {
-  int64_t blocks = (n_rows + n2v::kWavesPerBlock - 1) / n2v::kWavesPerBlock;
-  int64_t cap = n2v::resident_blocks((const void *)n2v::weighted_step_wave_kernel, n2v::kWavesPerBlock * 64, 0);
+int launch_weighted_step_wave(const n2v_graph *g, const int32_t *start_ids, int32_t num_walks, const int64_t *order,
+                              int64_t n_rows, int32_t min_n, int32_t step, int32_t walk_length, double p, double q,
+                              uint64_t seed, int64_t *edge_state, int32_t *walks, uint8_t *valid, uint32_t *status,
+                              hipStream_t stream) {
+  int64_t blocks = (n_rows + kWavesPerBlock - 1) / kWavesPerBlock;
   // (min_n == 0: `order` is the short list of the walkers the margin kernels left undecided, -1 behind the last --
   // a full grid of waves that each take one look at it cost 0.08 ms per step)
-  if (min_n <= 0 && cap > 1024) cap = 1024;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(n2v::weighted_step_wave_kernel, dim3((unsigned)blocks), dim3(n2v::kWavesPerBlock * 64), 0,
-                     (hipStream_t)stream, *g, start_ids, num_walks, order, n_rows, min_n, step, walk_length, p, q,
-                     seed, edge_state, walks, valid, status);
-  N2V_HIP_CHECK(hipGetLastError());
-  return N2V_OK;
+  if (min_n <= 0 && blocks > 1024) blocks = 1024;
+  return launch_status(launch_resident(weighted_step_wave_kernel, kWavesPerBlock * 64, 0, blocks, stream, *g,
+                                       start_ids, num_walks, order, n_rows, min_n, step, walk_length, p, q, seed,
+                                       edge_state, walks, valid, status));
 }
+
+}  // namespace n2v

@@ -19,7 +19,7 @@
 // candidate is accepted moves to its next step (or its next walker) at once, so
 // no lane waits for another's rejections: the wave only drains when the ballot of
 // live lanes is empty.  Uniforms: (seed, start vertex, ordinal, step, trial).
-#include "n2v_common.h"
+#include "n2v_walk_host.h"
 
 namespace n2v {
 
@@ -440,64 +440,35 @@ __global__ __launch_bounds__(256, 6) void walk_fast_kernel(
 
 }  // namespace n2v
 
-extern "C" int n2v_walk_fast_launch(const n2v_graph *g, const int32_t *start_ids,
-                                    int64_t n_start, int32_t num_walks, int32_t walk_length,
-                                    double p, double q, uint64_t seed, int32_t *walks_out,
-                                    uint8_t *valid_out, uint32_t *status, void *stream) {
-  const int64_t total = n_start * (int64_t)num_walks;
-  if (total == 0) return N2V_OK;
+// weighted graphs draw candidates from the K1 slots (the dispatcher saw them); unit-weight graphs from col itself
+namespace n2v {
+int launch_walk_fast(const WalkArgs &a) {
+  const n2v_graph *g = a.g;
   const bool unit = g->w == nullptr && g->w64 == nullptr;
-  if (!unit && !g->slots) return N2V_EINVAL;
-  const int threads = 256;
-  int64_t blocks = (total + threads - 1) / threads;
   const bool hops = unit && g->hops != nullptr;
   // class-first sampling: counts, return position and shared positions of every edge at hand
   const bool cf = unit && (hops || g->edge_classes) && g->wedge_off && g->wedge_pos &&
-                  !(p == 1.0 && q == 1.0);
-  const bool slots = cf && hops && q < 1.0 && g->wedge_slots && g->wedge_wide != 1;
-  const void *fn = slots  ? (const void *)n2v::walk_fast_kernel<true, true, true, true>
-                   : cf   ? (hops ? (const void *)n2v::walk_fast_kernel<true, true, true>
-                                  : (const void *)n2v::walk_fast_kernel<true, false, true>)
-                   : hops ? (const void *)n2v::walk_fast_kernel<true, true, false>
-                   : unit ? (const void *)n2v::walk_fast_kernel<true, false, false>
-                          : (const void *)n2v::walk_fast_kernel<false, false, false>;
-  const int64_t cap = n2v::resident_blocks(fn, threads, 0);
-  if (blocks > cap) blocks = cap;
+                  !(a.p == 1.0 && a.q == 1.0);
+  const bool slots = cf && hops && a.q < 1.0 && g->wedge_slots && g->wedge_wide != 1;
+  const auto kernel = slots  ? walk_fast_kernel<true, true, true, true>
+                      : cf   ? (hops ? walk_fast_kernel<true, true, true> : walk_fast_kernel<true, false, true>)
+                      : hops ? walk_fast_kernel<true, true, false>
+                      : unit ? walk_fast_kernel<true, false, false>
+                             : walk_fast_kernel<false, false, false>;
+  const int threads = 256;
   // status[2..3]: 64-bit trial counter (include/n2v_hip.h)
-  unsigned long long *trials = reinterpret_cast<unsigned long long *>(status + 2);
-#define N2V_FAST_LAUNCH(U, H, C)                                                                  \
-  hipLaunchKernelGGL((n2v::walk_fast_kernel<U, H, C>), dim3((unsigned)blocks), dim3(threads), 0, \
-                     (hipStream_t)stream, *g, start_ids, n_start, num_walks, walk_length, p, q,  \
-                     seed, walks_out, valid_out, status, trials)
-  if (slots)
-    hipLaunchKernelGGL((n2v::walk_fast_kernel<true, true, true, true>), dim3((unsigned)blocks),
-                       dim3(threads), 0, (hipStream_t)stream, *g, start_ids, n_start, num_walks,
-                       walk_length, p, q, seed, walks_out, valid_out, status, trials);
-  else if (cf && hops)
-    N2V_FAST_LAUNCH(true, true, true);
-  else if (cf)
-    N2V_FAST_LAUNCH(true, false, true);
-  else if (hops)
-    N2V_FAST_LAUNCH(true, true, false);
-  else if (unit)
-    N2V_FAST_LAUNCH(true, false, false);
-  else
-    N2V_FAST_LAUNCH(false, false, false);
-#undef N2V_FAST_LAUNCH
-  N2V_HIP_CHECK(hipGetLastError());
-  return N2V_OK;
+  unsigned long long *trials = reinterpret_cast<unsigned long long *>(a.status + 2);
+  return launch_status(launch_resident(kernel, threads, 0, (a.total() + threads - 1) / threads, a.stream, *g,
+                                       a.start_ids, a.n_start, a.num_walks, a.walk_length, a.p, a.q, a.seed,
+                                       a.walks_out, a.valid_out, a.status, trials));
 }
+}  // namespace n2v
 
 extern "C" int n2v_pivots_build(const int32_t *col, int64_t n_edges, int32_t *pivots_out,
                                 void *stream) {
   if (n_edges < 0 || (n_edges > 0 && (!col || !pivots_out))) return N2V_EINVAL;
   if (n_edges == 0) return N2V_OK;
   const int64_t n_blocks = (n_edges + 31) >> 5;
-  int64_t blocks = (n_blocks + 255) / 256;
-  const int64_t cap = n2v::resident_blocks((const void *)n2v::pivots_build_kernel, 256, 0) * 2;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(n2v::pivots_build_kernel, dim3((unsigned)blocks), dim3(256), 0,
-                     (hipStream_t)stream, col, n_edges, pivots_out);
-  N2V_HIP_CHECK(hipGetLastError());
-  return N2V_OK;
+  return n2v::launch_status(n2v::launch_resident<2>(n2v::pivots_build_kernel, 256, 0, (n_blocks + 255) / 256,
+                                                    (hipStream_t)stream, col, n_edges, pivots_out));
 }

@@ -42,7 +42,7 @@
 //     16-byte hop entry on any graph the ranked form accepts, no escape read: what serves vertex-id
 //     output where the field widths of the 8-byte hop table (hops8) do not fit the graph (cfg 4).
 // Same uniform stream as every other kernel (step_bits, n2v_common.h): bit-identical walks.
-#include "n2v_common.h"
+#include "n2v_walk_host.h"
 
 namespace n2v {
 
@@ -300,83 +300,33 @@ __global__ __launch_bounds__(kThreads) void walk_chunk_transpose_kernel(int32_t 
   }
 }
 
-// one launch of walk_uniform_kernel<kHops, kThreads, kChunked> over as many blocks as are resident
-template <int kHops, int kThreads, bool kChunked>
-static hipError_t launch_walk_uniform(const n2v_graph *g, const int32_t *start_ids, int64_t n_start,
-                                      int32_t num_walks, int32_t walk_length, uint64_t seed, int32_t *walks_out,
-                                      uint8_t *valid_out, uint32_t *status, size_t lds, hipStream_t stream) {
-  const auto fn = walk_uniform_kernel<kHops, kThreads, kChunked>;
-  int64_t blocks = (n_start * (int64_t)num_walks + kThreads - 1) / kThreads;
-  const int64_t cap = resident_blocks((const void *)fn, kThreads, lds);
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kThreads), lds, stream, *g, start_ids, n_start, num_walks,
-                     walk_length, seed, walks_out, valid_out, status);
-  return hipGetLastError();
+template <int kHops, int kThreads>
+static auto uniform_instance(bool chunked) {
+  return chunked ? walk_uniform_kernel<kHops, kThreads, true> : walk_uniform_kernel<kHops, kThreads, false>;
+}
+
+// `form`: the table that serves (the dispatcher checked its fields) -- 4 the 8-byte {id, rank} pairs, 3 the 4-byte
+// ranks, 2 hops8, 1 hops, 0 rowptr and col
+int launch_walk_uniform(const WalkArgs &a, int form) {
+  const int L1 = a.walk_length + 1;
+  const bool chunked = L1 <= kChunkMaxL1;
+  const auto kernel = form == 4   ? uniform_instance<4, 1024>(chunked)
+                      : form == 3 ? uniform_instance<3, 1024>(chunked)
+                      : form == 2 ? uniform_instance<2, 256>(chunked)
+                      : form == 1 ? uniform_instance<1, 256>(chunked)
+                                  : uniform_instance<0, 256>(chunked);
+  const int threads = form >= 3 ? 1024 : 256;
+  const size_t lds = form >= 3 ? (size_t)a.g->rank_classes * 8 : 0;
+  const int64_t total = a.total();
+  if (launch_resident(kernel, threads, lds, (total + threads - 1) / threads, a.stream, *a.g, a.start_ids, a.n_start,
+                      a.num_walks, a.walk_length, a.seed, a.walks_out, a.valid_out, a.status) != hipSuccess)
+    return N2V_ELAUNCH;
+  if (!chunked) return N2V_OK;
+  // the regions the walk kernel wrote step-major, row-major in place: walks_out is complete when the
+  // stream has passed this second kernel
+  return launch_status(launch_resident(walk_chunk_transpose_kernel<kTransposeThreads, kTransposeBatch>,
+                                       kTransposeThreads, (size_t)64 * (size_t)L1 * sizeof(int32_t),
+                                       (total + 63) / 64 /* < 2^26 */, a.stream, a.walks_out, total, L1));
 }
 
 }  // namespace n2v
-
-// returns 1 when the kernel applies (and was launched), 0 when it does not, < 0 on error
-extern "C" int n2v_walk_uniform_try(const n2v_graph *g, const int32_t *start_ids, int64_t n_start,
-                                    int32_t num_walks, int32_t walk_length, double p, double q,
-                                    uint64_t seed, int32_t *walks_out, uint8_t *valid_out,
-                                    uint32_t *status, void *stream) {
-  if (g->w != nullptr || g->w64 != nullptr || p != 1.0 || q != 1.0) return 0;
-  const int64_t total = n_start * (int64_t)num_walks;
-  if (total >= 0xffffff00ll) return 0;
-  if (total == 0) return 1;
-  // which table serves, and its argument checks: before anything is put on the stream.  rank_emit says what
-  // rank_hops points at: 0 / 1 the 4-byte ranks (vertex ids / ranks out), 2 the 8-byte {id, rank} pairs
-  const int form = g->rank_hops ? (g->rank_emit == 2 ? 4 : 3) : g->hops8 ? 2 : (g->hops ? 1 : 0);
-  if (form >= 3) {
-    const int P = g->rank_classes;
-    if (P < 2 || P > 8192 || (P & (P - 1)) || !g->rank_of || !g->rank_class_first || !g->rank_class_off ||
-        g->n_edges >= (1ll << 32) ||
-        g->rank_head_n < 0 || g->rank_head_n > (1 << 22) || (g->rank_head_n > 0 && !g->rank_head) ||
-        (g->rank_emit == 0 && !g->rank_vertex) || g->rank_emit < 0 || g->rank_emit > 2)
-      return N2V_EINVAL;
-  }
-  if (form == 2 && (g->hop8_col_bits < 1 || g->hop8_row_bits < 1 ||
-                    g->hop8_col_bits + g->hop8_row_bits > 62 || g->hop8_align_shift < 0 ||
-                    g->hop8_align_shift > 6 || (g->hop8_align_shift > 0 && !g->hop8_rowptr)))
-    return N2V_EINVAL;
-  // status[1] is the kernel's walker counter: start it at zero on the same stream
-  if (hipMemsetAsync(status + 1, 0, sizeof(uint32_t), (hipStream_t)stream) != hipSuccess)
-    return N2V_ELAUNCH;
-  const hipStream_t s = (hipStream_t)stream;
-  const size_t lds = form >= 3 ? (size_t)g->rank_classes * 8 : 0;
-  const bool chunked = walk_length + 1 <= n2v::kChunkMaxL1;
-  hipError_t e = hipSuccess;
-#define N2V_UNIFORM_LAUNCH(F, T)                                                                             \
-  e = chunked ? n2v::launch_walk_uniform<F, T, true>(g, start_ids, n_start, num_walks, walk_length, seed,    \
-                                                     walks_out, valid_out, status, lds, s)                   \
-              : n2v::launch_walk_uniform<F, T, false>(g, start_ids, n_start, num_walks, walk_length, seed,   \
-                                                      walks_out, valid_out, status, lds, s)
-  if (form == 4)
-    N2V_UNIFORM_LAUNCH(4, 1024);
-  else if (form == 3)
-    N2V_UNIFORM_LAUNCH(3, 1024);
-  else if (form == 2)
-    N2V_UNIFORM_LAUNCH(2, 256);
-  else if (form == 1)
-    N2V_UNIFORM_LAUNCH(1, 256);
-  else
-    N2V_UNIFORM_LAUNCH(0, 256);
-#undef N2V_UNIFORM_LAUNCH
-  if (e != hipSuccess) return N2V_ELAUNCH;
-  if (chunked) {
-    // the regions the walk kernel wrote step-major, row-major in place: walks_out is complete when the
-    // stream has passed this second kernel
-    int64_t chunks = (total + 63) / 64;  // < 2^26
-    const size_t tile = (size_t)64 * (size_t)(walk_length + 1) * sizeof(int32_t);
-    const int64_t cap = n2v::resident_blocks(
-        (const void *)n2v::walk_chunk_transpose_kernel<n2v::kTransposeThreads, n2v::kTransposeBatch>,
-        n2v::kTransposeThreads, tile);
-    if (chunks > cap) chunks = cap;
-    hipLaunchKernelGGL((n2v::walk_chunk_transpose_kernel<n2v::kTransposeThreads, n2v::kTransposeBatch>),
-                       dim3((unsigned)chunks), dim3(n2v::kTransposeThreads),
-                       tile, s, walks_out, total, walk_length + 1);
-    if (hipGetLastError() != hipSuccess) return N2V_ELAUNCH;
-  }
-  return 1;
-}

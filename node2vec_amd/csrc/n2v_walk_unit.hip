@@ -1542,6 +1542,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, kLanesWaves) void walk_exact_u
 
 }  // namespace n2v
 
+namespace n2v {
+
 // true when x * 2^20 is an exact integer in [0, 2^31): the integer-sum argument holds
 static bool scales_exactly(double x, int64_t *t_out) {
   const double t = x * 1048576.0;
@@ -1550,16 +1552,15 @@ static bool scales_exactly(double x, int64_t *t_out) {
   return true;
 }
 
-// the per-(p, q) constants of the unit-weight kernels; false = the pair is outside their range
-static bool unit_consts(double p, double q, n2v::UnitConsts &K, bool &dyadic) {
+bool unit_consts(double p, double q, UnitConsts &K) {
   K.bR = 1.0 / p;  // the reference's weight / return_param with weight == 1.0
   K.bM = 1.0;
   K.bO = 1.0 / q;
   K.TR = K.TM = K.TO = 0;
   // dyadic 1/p, 1/q: the row sum is an integer combination of three counts; otherwise it is
   // added up in the reference's order, run by run (needs ordinary magnitudes)
-  dyadic = scales_exactly(K.bR, &K.TR) && scales_exactly(K.bM, &K.TM) &&
-           scales_exactly(K.bO, &K.TO) && K.TR != 0 && K.TO != 0;
+  const bool dyadic = scales_exactly(K.bR, &K.TR) && scales_exactly(K.bM, &K.TM) &&
+                      scales_exactly(K.bO, &K.TO) && K.TR != 0 && K.TO != 0;
   K.gR = K.TR;
   K.gM = K.TM;
   K.gO = K.TO;
@@ -1582,8 +1583,33 @@ static bool unit_consts(double p, double q, n2v::UnitConsts &K, bool &dyadic) {
   return dyadic || ordinary;
 }
 
-int n2v_edge_row_sums_launch(const n2v_graph *g, const n2v::UnitConsts &K, double q, const int64_t *edges, int64_t k,
-                             double *sums_out, void *stream);
+// one lane per walker with the wave as fallback
+int launch_walk_unit_lanes(const WalkArgs &a, const UnitConsts &K) {
+  const auto kernel = a.g->hops ? walk_exact_unit_lanes_kernel<true> : walk_exact_unit_lanes_kernel<false>;
+  return launch_status(launch_resident(kernel, kWavesPerBlock * 64, 0, (a.total() + 255) / 256, a.stream, *a.g,
+                                       a.start_ids, a.n_start, a.num_walks, a.walk_length, a.p, a.q, K, a.seed,
+                                       a.walks_out, a.valid_out, a.status));
+}
+
+// one wave per walker, a persistent grid: exactly the resident capacity, walkers are grid-strided
+int launch_walk_unit_wave(const WalkArgs &a, const UnitConsts &K) {
+  const auto kernel = K.dyadic ? walk_exact_unit_kernel<true> : walk_exact_unit_kernel<false>;
+  return launch_status(launch_resident(kernel, kWavesPerBlock * 64, 0,
+                                       (a.total() + kWavesPerBlock - 1) / kWavesPerBlock, a.stream, *a.g,
+                                       a.start_ids, a.n_start, a.num_walks, a.walk_length, a.p, a.q, K, a.seed,
+                                       a.walks_out, a.valid_out, a.status));
+}
+
+// the unit-weight instance of n2v_partition_step: the row of the previous vertex travelled
+int launch_step_unit(const StepArgs &a, const UnitConsts &K) {
+  const auto kernel = K.dyadic ? partition_step_unit_kernel<true> : partition_step_unit_kernel<false>;
+  return launch_status(launch_resident(kernel, kWavesPerBlock * 64, 0, (a.k + kWavesPerBlock - 1) / kWavesPerBlock,
+                                       a.stream, a.rowptr, a.col, a.lo, a.n_local, a.head, (int)a.head_cols,
+                                       a.src_ptr, a.src_ids, a.k, a.p, a.q, K, a.seed, a.next_out, a.edge_out,
+                                       a.status));
+}
+
+}  // namespace n2v
 
 extern "C" int n2v_edge_row_sums_build(const n2v_graph *g, double p, double q, const int64_t *edges, int64_t k,
                                        double *sums_out, void *stream) {
@@ -1593,120 +1619,6 @@ extern "C" int n2v_edge_row_sums_build(const n2v_graph *g, double p, double q, c
       !sums_out || g->wedge_wide < 0 || g->wedge_wide > 65536)
     return N2V_EINVAL;
   n2v::UnitConsts K;
-  bool dyadic = false;
-  if (!unit_consts(p, q, K, dyadic)) return N2V_EINVAL;
-  return n2v_edge_row_sums_launch(g, K, q, edges, k, sums_out, stream);
+  if (!n2v::unit_consts(p, q, K)) return N2V_EINVAL;
+  return n2v::launch_edge_row_sums(g, K, q, edges, k, sums_out, (hipStream_t)stream);
 }
-
-// returns 1 when the unit-weight kernel applies (and was launched), 0 when the caller
-// must use the generic kernel, < 0 on error
-extern "C" int n2v_walk_exact_unit_try(const n2v_graph *g, const int32_t *start_ids,
-                                       int64_t n_start, int32_t num_walks,
-                                       int32_t walk_length, double p, double q, uint64_t seed,
-                                       int32_t *walks_out, uint8_t *valid_out, uint32_t *status,
-                                       void *stream) {
-  if (g->w != nullptr || g->w64 != nullptr) return 0;
-  n2v::UnitConsts K;
-  bool dyadic = false;
-  if (!unit_consts(p, q, K, dyadic)) return 0;
-  const int64_t total = n_start * (int64_t)num_walks;
-  if (total == 0) return 1;
-  // status[1] is the kernels' walker counter: start it at zero on the same stream
-  if (hipMemsetAsync(status + 1, 0, sizeof(uint32_t), (hipStream_t)stream) != hipSuccess)
-    return N2V_ELAUNCH;
-  // lanes kernel: dyadic p, q with the per-edge class counts at hand (p == q == 1 needs none),
-  // when the "other" class -- nearly every slot of a row -- is the underfull one: 1/q <= 1 and
-  // 1/p >= 1/q.  Then ~80 % of the steps leave through the per-lane exits.  For the other
-  // arrangements (q < 1, or p > q) the usual `pick` is an overfull slot, every step needs the
-  // pairing, and one wave per walker (below) is the better shape (measured: cfg 2, p = 4,
-  // q = 0.25: 344 against 241 M steps/s; p = 2, q = 1: 938 against 711).
-  const bool lanes_regime = (p == 1.0 && q == 1.0) || (K.bO <= 1.0 && K.bR >= K.bO);
-  // every dyadic (p, q) has its pairing in closed form (n2v_unit_core.h): "other" alone on its
-  // stack -- the only underfull class (1/q <= 1, 1/p >= 1/q) or the only overfull one (1/q >= 1,
-  // 1/p <= 1/q; with p == q the return slot is an "other" slot) --, or sharing it with the return
-  // run (q > 1 with p > q; q < 1 with p < q)
-  // (values that are not dyadic: the same kernel adds the row up in the reference's order and
-  // replays every pairing run by run)
-  if (!(p == 1.0 && q == 1.0) && !(g->reserved & 1)) {
-    // every per-edge table is at hand: the kernel in which no step needs the wave
-    const int rw = n2v_walk_wedge_try(g, start_ids, n_start, num_walks, walk_length, p, q, K, seed,
-                                      walks_out, valid_out, status, stream);
-    if (rw != 0) return rw;
-  }
-  // (a hop table with inline return positions is read by the slots kernel alone)
-  if (g->hops && (g->reserved2 & N2V_HOPS_INLINE_RPOS) && !(p == 1.0 && q == 1.0)) return N2V_EINVAL;
-  if (dyadic && lanes_regime && total < 0xffffff00ll &&
-      (g->edge_classes || g->hops || (p == 1.0 && q == 1.0))) {
-    int64_t blocks = (total + 255) / 256;
-    const void *lfn = g->hops ? (const void *)n2v::walk_exact_unit_lanes_kernel<true>
-                              : (const void *)n2v::walk_exact_unit_lanes_kernel<false>;
-    const int64_t cap = n2v::resident_blocks(lfn, n2v::kWavesPerBlock * 64, 0);
-    if (blocks > cap) blocks = cap;
-    if (g->hops)
-      hipLaunchKernelGGL(n2v::walk_exact_unit_lanes_kernel<true>, dim3((unsigned)blocks),
-                         dim3(n2v::kWavesPerBlock * 64), 0, (hipStream_t)stream, *g, start_ids,
-                         n_start, num_walks, walk_length, p, q, K, seed, walks_out, valid_out,
-                         status);
-    else
-      hipLaunchKernelGGL(n2v::walk_exact_unit_lanes_kernel<false>, dim3((unsigned)blocks),
-                         dim3(n2v::kWavesPerBlock * 64), 0, (hipStream_t)stream, *g, start_ids,
-                         n_start, num_walks, walk_length, p, q, K, seed, walks_out, valid_out,
-                         status);
-    if (hipGetLastError() != hipSuccess) return N2V_ELAUNCH;
-    return 1;
-  }
-  // persistent grid: exactly the resident capacity, walkers are grid-strided
-  int64_t blocks = (total + n2v::kWavesPerBlock - 1) / n2v::kWavesPerBlock;
-  const void *fn = dyadic ? (const void *)n2v::walk_exact_unit_kernel<true>
-                          : (const void *)n2v::walk_exact_unit_kernel<false>;
-  const int64_t cap = n2v::resident_blocks(fn, n2v::kWavesPerBlock * 64, 0);
-  if (blocks > cap) blocks = cap;
-  if (dyadic)
-    hipLaunchKernelGGL(n2v::walk_exact_unit_kernel<true>, dim3((unsigned)blocks),
-                       dim3(n2v::kWavesPerBlock * 64), 0, (hipStream_t)stream, *g, start_ids,
-                       n_start, num_walks, walk_length, p, q, K, seed, walks_out, valid_out,
-                       status);
-  else
-    hipLaunchKernelGGL(n2v::walk_exact_unit_kernel<false>, dim3((unsigned)blocks),
-                       dim3(n2v::kWavesPerBlock * 64), 0, (hipStream_t)stream, *g, start_ids,
-                       n_start, num_walks, walk_length, p, q, K, seed, walks_out, valid_out,
-                       status);
-  if (hipGetLastError() != hipSuccess) return N2V_ELAUNCH;
-  return 1;
-}
-
-// the unit-weight instance of n2v_partition_step (n2v_walk.hip calls it first): 1 = launched,
-// 0 = (p, q) outside the unit kernels' range, < 0 on error.  status[1] was zeroed by the caller.
-extern "C" int n2v_partition_step_unit_try(const int64_t *rowptr, const int32_t *col, int64_t lo,
-                                           int64_t n_local, const int64_t *head, int32_t head_cols,
-                                           const int64_t *src_ptr, const int32_t *src_ids,
-                                           int32_t wedge_lists, int64_t k, double p, double q,
-                                           uint64_t seed, int32_t *next_out, int64_t *edge_out,
-                                           uint32_t *status, void *stream) {
-  n2v::UnitConsts K;
-  bool dyadic = false;
-  if (!unit_consts(p, q, K, dyadic)) return 0;
-  if (wedge_lists)  // one lane per walker, the closed forms of the wedge kernel
-    return n2v_partition_step_wedge_launch(rowptr, col, lo, n_local, head, head_cols, src_ptr,
-                                           src_ids, wedge_lists == 2, k, p, q, K, seed, next_out,
-                                           edge_out, status, stream);
-  int64_t blocks = (k + n2v::kWavesPerBlock - 1) / n2v::kWavesPerBlock;
-#define N2V_PART_LAUNCH(D)                                                                        \
-  do {                                                                                           \
-    const int64_t cap = n2v::resident_blocks((const void *)n2v::partition_step_unit_kernel<D>,   \
-                                             n2v::kWavesPerBlock * 64, 0);                       \
-    if (blocks > cap) blocks = cap;                                                              \
-    hipLaunchKernelGGL(n2v::partition_step_unit_kernel<D>, dim3((unsigned)blocks),               \
-                       dim3(n2v::kWavesPerBlock * 64), 0, (hipStream_t)stream, rowptr, col, lo,  \
-                       n_local, head, (int)head_cols, src_ptr, src_ids, k, p, q, K, seed,        \
-                       next_out, edge_out, status);                                              \
-  } while (0)
-  if (dyadic)
-    N2V_PART_LAUNCH(true);
-  else
-    N2V_PART_LAUNCH(false);
-#undef N2V_PART_LAUNCH
-  if (hipGetLastError() != hipSuccess) return N2V_ELAUNCH;
-  return 1;
-}
-

@@ -490,85 +490,51 @@ __global__ __launch_bounds__(kWedgeThreads, kWedgeWaves) void partition_step_wed
 
 }  // namespace n2v
 
-// returns 1 when the kernel applies (and was launched), 0 when it does not, < 0 on error
-int n2v_walk_wedge_try(const n2v_graph *g, const int32_t *start_ids, int64_t n_start,
-                       int32_t num_walks, int32_t walk_length, double p, double q,
-                       const n2v::UnitConsts &K, uint64_t seed, int32_t *walks_out,
-                       uint8_t *valid_out, uint32_t *status, void *stream) {
-  if (!g->hops || !g->wedge_off || !g->wedge_pos || g->w || g->w64) return 0;
-  const int64_t total = n_start * (int64_t)num_walks;
-  if (total >= 0xffffff00ll) return 0;
-  if (total == 0) return 1;
-  // the return run shares a stack with "other" on ordinary rows: q > 1 with p > q, q < 1 with p < q
+namespace n2v {
+
+// the instance <kMode> of a kernel for the arrangement of the classes on the two stacks at (p, q): 2 for values
+// that are not dyadic; else 0 "other" alone underfull, 3 "other" alone overfull, 1 the return run shares a stack
+// with "other" on ordinary rows (q > 1 with p > q, q < 1 with p < q)
+template <typename F>
+static F *by_mode(const UnitConsts &K, F *m0, F *m1, F *m2, F *m3) {
   const bool alone_under = K.bO <= 1.0 && K.bR >= K.bO, alone_over = K.bO >= 1.0 && K.bR <= K.bO;
-  if (g->wedge_wide < 0 || g->wedge_wide > 65536) return N2V_EINVAL;
-  // (a mixed table -- rows of wedge_wide slots and more -- goes to the slots kernel with FOLDED slots only)
-  if (g->wedge_slots && g->wedge_wide != 1 && !(g->reserved & 2) &&
-      (g->wedge_wide == 0 || (g->reserved2 & N2V_SLOTS_FOLDED))) {
-    n2v_graph gs = *g;  // the table of row sums counts for the (p, q) it was built for only
-    if (K.dyadic || gs.row_sums == nullptr || !(gs.row_sums_p == p && gs.row_sums_q == q) || gs.row_sums_from < 1)
-      gs.row_sums = nullptr;
-    g = &gs;
-    // the wedge slots are at hand: the list of a step arrives with its hop entry
-    auto sk = !K.dyadic    ? n2v::walk_exact_wedge_slots_kernel<2>
-              : alone_under ? n2v::walk_exact_wedge_slots_kernel<0>
-              : alone_over  ? n2v::walk_exact_wedge_slots_kernel<3>
-                            : n2v::walk_exact_wedge_slots_kernel<1>;
-    int64_t sblocks = (total + n2v::kWedgeThreads - 1) / n2v::kWedgeThreads;
-    const int64_t scap = n2v::resident_blocks((const void *)sk, n2v::kWedgeThreads, 0);
-    if (sblocks > scap) sblocks = scap;
-    hipLaunchKernelGGL(sk, dim3((unsigned)sblocks), dim3(n2v::kWedgeThreads), 0, (hipStream_t)stream,
-                       *g, start_ids, n_start, num_walks, walk_length, q, K, seed, walks_out,
-                       valid_out, status);
-    if (hipGetLastError() != hipSuccess) return N2V_ELAUNCH;
-    return 1;
-  }
-  if (g->reserved2 & N2V_HOPS_INLINE_RPOS) return N2V_EINVAL;  // that hop table is the slots kernel's
-  n2v_graph gp = *g;
-  gp.row_sums = nullptr;  // (this kernel adds every row up itself)
-  g = &gp;
-  auto kernel = !K.dyadic    ? n2v::walk_exact_wedge_kernel<2>
-                : alone_under ? n2v::walk_exact_wedge_kernel<0>
-                : alone_over  ? n2v::walk_exact_wedge_kernel<3>
-                              : n2v::walk_exact_wedge_kernel<1>;
-  int64_t blocks = (total + n2v::kWedgeThreads - 1) / n2v::kWedgeThreads;
-  const int64_t cap = n2v::resident_blocks((const void *)kernel, n2v::kWedgeThreads, 0);
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(n2v::kWedgeThreads), 0,
-                     (hipStream_t)stream, *g, start_ids, n_start, num_walks, walk_length, p, q, K, seed,
-                     walks_out, valid_out, status);
-  if (hipGetLastError() != hipSuccess) return N2V_ELAUNCH;
-  return 1;
+  return !K.dyadic ? m2 : alone_under ? m0 : alone_over ? m3 : m1;
 }
 
-// the wedge-list instance of n2v_partition_step: 1 = launched, < 0 on error
-int n2v_partition_step_wedge_launch(const int64_t *rowptr, const int32_t *col, int64_t lo,
-                                    int64_t n_local, const int64_t *head, int32_t head_cols,
-                                    const int64_t *src_ptr, const int32_t *src_ids, int32_t src_at,
-                                    int64_t k, double p, double q, const n2v::UnitConsts &K, uint64_t seed,
-                                    int32_t *next_out, int64_t *edge_out, uint32_t *status,
-                                    void *stream) {
-  const bool biased = !(p == 1.0 && q == 1.0);  // p == q == 1: the header's first four words do
-  if (biased && (head_cols < 5 || !src_ptr || !src_ids)) return N2V_EINVAL;
-  const bool alone_under = K.bO <= 1.0 && K.bR >= K.bO, alone_over = K.bO >= 1.0 && K.bR <= K.bO;
-  auto kernel = !K.dyadic    ? n2v::partition_step_wedge_kernel<2>
-                : alone_under ? n2v::partition_step_wedge_kernel<0>
-                : alone_over  ? n2v::partition_step_wedge_kernel<3>
-                              : n2v::partition_step_wedge_kernel<1>;
-  int64_t blocks = (k + n2v::kWedgeThreads - 1) / n2v::kWedgeThreads;
-  const int64_t cap = n2v::resident_blocks((const void *)kernel, n2v::kWedgeThreads, 0);
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(n2v::kWedgeThreads), 0, (hipStream_t)stream,
-                     rowptr, col, lo, n_local, head, (int)head_cols, src_ptr, src_ids, (int)src_at, k, p, q, K,
-                     seed, next_out, edge_out, status);
-  if (hipGetLastError() != hipSuccess) return N2V_ELAUNCH;
-  return 1;
+// the wedge slots are at hand: the list of a step arrives with its hop entry
+int launch_walk_wedge_slots(const WalkArgs &a, const UnitConsts &K) {
+  n2v_graph g = *a.g;  // the table of row sums counts for the (p, q) it was built for only
+  if (K.dyadic || !(g.row_sums_p == a.p && g.row_sums_q == a.q) || g.row_sums_from < 1) g.row_sums = nullptr;
+  const auto kernel = by_mode(K, walk_exact_wedge_slots_kernel<0>, walk_exact_wedge_slots_kernel<1>,
+                              walk_exact_wedge_slots_kernel<2>, walk_exact_wedge_slots_kernel<3>);
+  return launch_status(launch_resident(kernel, kWedgeThreads, 0, (a.total() + kWedgeThreads - 1) / kWedgeThreads,
+                                       a.stream, g, a.start_ids, a.n_start, a.num_walks, a.walk_length, a.q, K,
+                                       a.seed, a.walks_out, a.valid_out, a.status));
+}
+
+int launch_walk_wedge(const WalkArgs &a, const UnitConsts &K) {
+  n2v_graph g = *a.g;
+  g.row_sums = nullptr;  // (this kernel adds every row up itself)
+  const auto kernel = by_mode(K, walk_exact_wedge_kernel<0>, walk_exact_wedge_kernel<1>, walk_exact_wedge_kernel<2>,
+                              walk_exact_wedge_kernel<3>);
+  return launch_status(launch_resident(kernel, kWedgeThreads, 0, (a.total() + kWedgeThreads - 1) / kWedgeThreads,
+                                       a.stream, g, a.start_ids, a.n_start, a.num_walks, a.walk_length, a.p, a.q, K,
+                                       a.seed, a.walks_out, a.valid_out, a.status));
+}
+
+// the wedge-list instance of n2v_partition_step
+int launch_step_wedge(const StepArgs &a, const UnitConsts &K) {
+  const auto kernel = by_mode(K, partition_step_wedge_kernel<0>, partition_step_wedge_kernel<1>,
+                              partition_step_wedge_kernel<2>, partition_step_wedge_kernel<3>);
+  return launch_status(launch_resident(kernel, kWedgeThreads, 0, (a.k + kWedgeThreads - 1) / kWedgeThreads, a.stream,
+                                       a.rowptr, a.col, a.lo, a.n_local, a.head, (int)a.head_cols, a.src_ptr,
+                                       a.src_ids, (int)(a.src_kind == N2V_SRC_WEDGES_AT), a.k, a.p, a.q, K, a.seed,
+                                       a.next_out, a.edge_out, a.status));
 }
 
 // ---- row sums of the tables of the steps into long rows, for one (p, q) that is not dyadic (include/n2v_hip.h,
 // n2v_edge_row_sums_build): lane_row_sum -- the routine a step of walk_exact_wedge_slots_kernel<2> would run -- once
 // per edge, one lane per edge of the caller's list
-namespace n2v {
 __global__ __launch_bounds__(256) void edge_row_sums_kernel(n2v_graph g, UnitConsts K, bool merge_r, bool need_mem,
                                                             const int64_t *__restrict__ edges, int64_t k,
                                                             double *__restrict__ out) {
@@ -596,15 +562,11 @@ __global__ __launch_bounds__(256) void edge_row_sums_kernel(n2v_graph g, UnitCon
     out[e] = sum;
   }
 }
-}  // namespace n2v
 
-int n2v_edge_row_sums_launch(const n2v_graph *g, const n2v::UnitConsts &K, double q, const int64_t *edges, int64_t k,
-                             double *sums_out, void *stream) {
-  int64_t blocks = (k + 255) / 256;
-  const int64_t cap = 4 * n2v::resident_blocks((const void *)n2v::edge_row_sums_kernel, 256, 0);
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(n2v::edge_row_sums_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *g, K,
-                     K.bR == K.bO, q != 1.0, edges, k, sums_out);
-  if (hipGetLastError() != hipSuccess) return N2V_ELAUNCH;
-  return N2V_OK;
+int launch_edge_row_sums(const n2v_graph *g, const UnitConsts &K, double q, const int64_t *edges, int64_t k,
+                         double *sums_out, hipStream_t stream) {
+  return launch_status(launch_resident<4>(edge_row_sums_kernel, 256, 0, (k + 255) / 256, stream, *g, K,
+                                          K.bR == K.bO, q != 1.0, edges, k, sums_out));
 }
+
+}  // namespace n2v

@@ -42,7 +42,7 @@
 //     weights of its current 8 slots in the lane's own LDS column.
 // Same uniform stream, same table, same draw as every other exact kernel: bit-identical walks
 // (tests/test_weighted_lanes_gpu.py: the fp64 goldens, the oracle, walk_exact_kernel over a batch).
-#include "n2v_common.h"
+#include "n2v_walk_host.h"
 
 namespace n2v {
 
@@ -460,7 +460,7 @@ __global__ __launch_bounds__(TH) void walk_weighted_step_kernel(
 //    2 (2 n + 4) 2^-53 per slot whose side of 1.0 cannot be told: together < 6 n^2 2^-53)
 // and a draw that any comparison cannot decide by that margin -- r2 against probs, a sum against the
 // sum it crosses, `pick` against 1.0 -- is NOT decided here: the walker goes on a list and the exact
-// wave kernel (n2v_weighted_step_wave_launch) steps it.  With real-valued weights that is one step in
+// wave kernel (launch_weighted_step_wave) steps it.  With real-valued weights that is one step in
 // ~10^6; rows whose sums tie exactly (few distinct weights) are undecided often and walk at the exact
 // kernel's rate.  Same draws either way.
 constexpr int kWmUndecided = -2;
@@ -1483,12 +1483,6 @@ __global__ __launch_bounds__(kWmWaves * 64, kWmWavesPerSimd) void walk_weighted_
 
 }  // namespace n2v
 
-extern "C" int n2v_weighted_step_wave_launch(const n2v_graph *g, const int32_t *start_ids, int32_t num_walks,
-                                             const int64_t *order, int64_t n_rows, int32_t min_n,
-                                             int32_t step, int32_t walk_length, double p, double q,
-                                             uint64_t seed, int64_t *edge_state, int32_t *walks,
-                                             uint8_t *valid, uint32_t *status, void *stream);
-
 // rows of up to this many slots: the 8-slot instance; longer ones: the 32-slot instance.  Measured on
 // cfg 2 (profiles/r7h_time_wlanes_two_instances.log, r7k_time_wlanes.log): the 32-slot instance (255 VGPRs,
 // one wave per SIMD) LOSES -- 15 - 25 M steps/s with the cut at 1 024 / 4 096 slots against 51 - 55 M with
@@ -1503,21 +1497,11 @@ static int wl_launch(const n2v_graph *g, const WT *w, const int32_t *start_ids, 
                      const int64_t *order, int64_t n_rows, int min_n, int max_n, int32_t step,
                      int32_t walk_length, const WlConsts &K, uint64_t seed, int64_t *edge_state,
                      int32_t *walks, uint8_t *valid, uint32_t *status, hipStream_t st) {
-  int64_t blocks = (n_rows + TH - 1) / TH;
-  const bool pow2 = K.p_pow2 && K.q_pow2;
-  const void *fn = pow2 ? (const void *)walk_weighted_step_kernel<WT, CH, TH, true>
-                        : (const void *)walk_weighted_step_kernel<WT, CH, TH, false>;
-  const int64_t cap = resident_blocks(fn, TH, 0);
-  if (blocks > cap) blocks = cap;
-  if (pow2)
-    hipLaunchKernelGGL((walk_weighted_step_kernel<WT, CH, TH, true>), dim3((unsigned)blocks), dim3(TH), 0, st, *g,
-                       w, start_ids, num_walks, order, n_rows, min_n, max_n, step, walk_length, K, seed,
-                       edge_state, walks, valid, status);
-  else
-    hipLaunchKernelGGL((walk_weighted_step_kernel<WT, CH, TH, false>), dim3((unsigned)blocks), dim3(TH), 0, st, *g,
-                       w, start_ids, num_walks, order, n_rows, min_n, max_n, step, walk_length, K, seed,
-                       edge_state, walks, valid, status);
-  return hipGetLastError() == hipSuccess ? N2V_OK : N2V_ELAUNCH;
+  const auto kernel = K.p_pow2 && K.q_pow2 ? walk_weighted_step_kernel<WT, CH, TH, true>
+                                           : walk_weighted_step_kernel<WT, CH, TH, false>;
+  return launch_status(launch_resident(kernel, TH, 0, (n_rows + TH - 1) / TH, st, *g, w, start_ids, num_walks, order,
+                                       n_rows, min_n, max_n, step, walk_length, K, seed, edge_state, walks, valid,
+                                       status));
 }
 }  // namespace n2v
 
@@ -1535,43 +1519,24 @@ static int wm_launch(const n2v_graph *g, const WT *w, const int32_t *start_ids, 
                      const WlConsts &K, uint64_t seed, int64_t *edge_state, int32_t *walks, uint8_t *valid,
                      uint32_t *status, int64_t *undecided, const double *row_sums, const n2v_weighted_hubs &hubs,
                      hipStream_t st) {
-  const bool pow2 = K.p_pow2 && K.q_pow2;
-  const void *fn = pow2 ? (const void *)walk_weighted_margin_kernel<WT, true, kSeq>
-                        : (const void *)walk_weighted_margin_kernel<WT, false, kSeq>;
+  const auto kernel = K.p_pow2 && K.q_pow2 ? walk_weighted_margin_kernel<WT, true, kSeq>
+                                           : walk_weighted_margin_kernel<WT, false, kSeq>;
   int64_t blocks = (n_rows + kWmWaves - 1) / kWmWaves;
-  int64_t cap = resident_blocks(fn, kWmWaves * 64, 0);
-  if (kSeq && cap > 1024) cap = 1024;  // (a list of a few walkers as a rule)
-  if (blocks > cap) blocks = cap;
-  if (pow2)
-    hipLaunchKernelGGL((walk_weighted_margin_kernel<WT, true, kSeq>), dim3((unsigned)blocks), dim3(kWmWaves * 64), 0,
-                       st, *g, w, start_ids, num_walks, order, n_rows, min_n, step, walk_length, K, seed, edge_state,
-                       walks, valid, status, undecided, row_sums, hubs);
-  else
-    hipLaunchKernelGGL((walk_weighted_margin_kernel<WT, false, kSeq>), dim3((unsigned)blocks), dim3(kWmWaves * 64), 0,
-                       st, *g, w, start_ids, num_walks, order, n_rows, min_n, step, walk_length, K, seed, edge_state,
-                       walks, valid, status, undecided, row_sums, hubs);
-  return hipGetLastError() == hipSuccess ? N2V_OK : N2V_ELAUNCH;
+  if (kSeq && blocks > 1024) blocks = 1024;  // (a list of a few walkers as a rule)
+  return launch_status(launch_resident(kernel, kWmWaves * 64, 0, blocks, st, *g, w, start_ids, num_walks, order,
+                                       n_rows, min_n, step, walk_length, K, seed, edge_state, walks, valid, status,
+                                       undecided, row_sums, hubs));
 }
 template <typename WT>
 static int lm_launch(const n2v_graph *g, const WT *w, const int32_t *start_ids, int32_t num_walks,
                      const int64_t *order, int64_t n_rows, int max_n, int32_t step, int32_t walk_length,
                      const WlConsts &K, uint64_t seed, int64_t *edge_state, int32_t *walks, uint8_t *valid,
                      uint32_t *status, int64_t *undecided, const double *row_sums, hipStream_t st) {
-  const bool pow2 = K.p_pow2 && K.q_pow2;
-  const void *fn = pow2 ? (const void *)walk_weighted_lane_margin_kernel<WT, true>
-                        : (const void *)walk_weighted_lane_margin_kernel<WT, false>;
-  int64_t blocks = (n_rows + 255) / 256;
-  const int64_t cap = resident_blocks(fn, 256, 0);
-  if (blocks > cap) blocks = cap;
-  if (pow2)
-    hipLaunchKernelGGL((walk_weighted_lane_margin_kernel<WT, true>), dim3((unsigned)blocks), dim3(256), 0, st, *g, w,
-                       start_ids, num_walks, order, n_rows, max_n, step, walk_length, K, seed, edge_state, walks, valid,
-                       status, undecided, row_sums);
-  else
-    hipLaunchKernelGGL((walk_weighted_lane_margin_kernel<WT, false>), dim3((unsigned)blocks), dim3(256), 0, st, *g, w,
-                       start_ids, num_walks, order, n_rows, max_n, step, walk_length, K, seed, edge_state, walks, valid,
-                       status, undecided, row_sums);
-  return hipGetLastError() == hipSuccess ? N2V_OK : N2V_ELAUNCH;
+  const auto kernel = K.p_pow2 && K.q_pow2 ? walk_weighted_lane_margin_kernel<WT, true>
+                                           : walk_weighted_lane_margin_kernel<WT, false>;
+  return launch_status(launch_resident(kernel, 256, 0, (n_rows + 255) / 256, st, *g, w, start_ids, num_walks, order,
+                                       n_rows, max_n, step, walk_length, K, seed, edge_state, walks, valid, status,
+                                       undecided, row_sums));
 }
 }  // namespace n2v
 
@@ -1698,14 +1663,14 @@ extern "C" int n2v_walk_weighted_step(const n2v_graph *g, const int32_t *start_i
                                               K, seed, edge_state, walks, valid, status, last, row_sums, hb, st);
     if (rc != N2V_OK) return rc;
     if (hipMemsetAsync(status + 1, 0, sizeof(uint32_t), st) != hipSuccess) return N2V_ELAUNCH;
-    rc = n2v_weighted_step_wave_launch(g, start_ids, num_walks, last + 1, n_rows, -1, step, walk_length,
-                                       return_param, inout_param, seed, edge_state, walks, valid, status, stream);
+    rc = n2v::launch_weighted_step_wave(g, start_ids, num_walks, last + 1, n_rows, -1, step, walk_length,
+                                        return_param, inout_param, seed, edge_state, walks, valid, status, st);
     if (rc != N2V_OK) return rc;
     return N2V_OK;  // (every row was one of the two margin kernels')
   } else if (order && wave_from != 0x7fffffff) {
     if (hipMemsetAsync(status + 1, 0, sizeof(uint32_t), st) != hipSuccess) return N2V_ELAUNCH;
-    rc = n2v_weighted_step_wave_launch(g, start_ids, num_walks, order, n_rows, wave_from - 1, step, walk_length,
-                                       return_param, inout_param, seed, edge_state, walks, valid, status, stream);
+    rc = n2v::launch_weighted_step_wave(g, start_ids, num_walks, order, n_rows, wave_from - 1, step, walk_length,
+                                        return_param, inout_param, seed, edge_state, walks, valid, status, st);
     if (rc != N2V_OK) return rc;
   }
   if (g->w64) {

@@ -26,7 +26,7 @@ def _dyadic(x: float) -> bool:
 
 def lanes_regime(p: float, q: float) -> bool:
     """The (p, q) for which exact walks on a unit-weight graph use the per-edge class counts
-    (same predicate as n2v_walk_exact_unit_try, csrc/n2v_walk_unit.hip): dyadic values with
+    (same predicate as dispatch_walk, csrc/n2v_capi.hip): dyadic values with
     1/q <= 1 and 1/p >= 1/q, i.e. the bulk of every row ("other" neighbours) is underfull."""
     return _dyadic(p) and _dyadic(q) and 1.0 / q <= 1.0 and 1.0 / p >= 1.0 / q
 
@@ -37,7 +37,7 @@ def tables_regime(p: float, q: float) -> bool:
     (which needs no table but the hop table).  Dyadic 1/p, 1/q: the pairing of a row has a closed
     form whether the bulk class "other" is alone on its stack (q >= 1 with p <= q, q <= 1 with
     p >= q) or shares it with the return slot; other values of ordinary magnitude (2^-20 .. 2^20,
-    the bound of n2v_walk_exact_unit_try): the row is summed in the reference's order and the
+    the bound of unit_consts, csrc/n2v_walk_unit.hip): the row is summed in the reference's order and the
     pairing replayed run by run, one lane per walker all the same."""
     if p == 1.0 and q == 1.0:
         return False
@@ -240,7 +240,7 @@ def walk(graph: DeviceGraph, start_ids: torch.Tensor, num_walks: int, walk_lengt
         g.wedge_pos = 0
         g.wedge_slots = 0
     if not use_wedge_kernel:  # keep the tables but walk with the lanes kernel (tests: same bits)
-        g.reserved = 1
+        g.reserved = _lib.DIAG_NO_TABLES_KERNEL
     if not use_wedge_slots:  # the all-tables kernel through wedge_off (tests: same bits)
         g.wedge_slots = 0
     if not use_row_sums:  # every row added up by the lane that needs its sum (tests: same bits)

@@ -3,6 +3,7 @@ include/n2v_hip.h declares (no compute calls here)."""
 import ctypes
 import os
 import re
+import struct
 
 from conftest import ROOT
 
@@ -27,6 +28,26 @@ def test_header_declares_the_expected_entry_points():
         assert want in names
 
 
+def _defined_dynamic_symbols(path):
+    """names of the defined symbols of the .dynsym section of a little-endian ELF64 file"""
+    data = open(path, "rb").read()
+    assert data[:6] == b"\x7fELF\x02\x01"
+    shoff, = struct.unpack_from("<Q", data, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", data, 0x3A)
+    # Elf64_Shdr: name, type, flags, addr, offset, size, link, info, addralign, entsize
+    sections = [struct.unpack_from("<IIQQQQIIQQ", data, shoff + i * shentsize) for i in range(shnum)]
+    names = set()
+    for _, sh_type, _, _, offset, size, link, _, _, entsize in sections:
+        if sh_type != 11:  # SHT_DYNSYM
+            continue
+        strtab = sections[link][4]
+        for at in range(offset, offset + size, entsize):
+            st_name, _, _, st_shndx = struct.unpack_from("<IBBH", data, at)  # Elf64_Sym, its first 8 bytes
+            if st_shndx != 0:  # SHN_UNDEF: imported, not defined here
+                names.add(data[strtab + st_name:data.index(b"\0", strtab + st_name)].decode())
+    return names
+
+
 def test_library_exports_every_declared_symbol():
     import __graft_entry__ as ge
 
@@ -37,6 +58,8 @@ def test_library_exports_every_declared_symbol():
     for name in _declared():
         assert hasattr(lib, name), name
     assert sorted(_lib.SYMBOLS) == _declared()
+    # and nothing else under the public prefix: functions shared between the library's own files have C++ linkage
+    assert sorted(s for s in _defined_dynamic_symbols(_lib.LIB_PATH) if s.startswith("n2v_")) == _declared()
     lib.n2v_abi_version.restype = ctypes.c_int
     assert lib.n2v_abi_version() == _lib.ABI_VERSION == 15
     lib.n2v_status_string.restype = ctypes.c_char_p
