@@ -1057,6 +1057,48 @@ int n2v_ivf_topk(const float *X, const float *inv_norm, int64_t n, int32_t dim, 
                  int64_t *out_rows, float *out_scores, uint32_t *status, void *workspace, int64_t workspace_bytes,
                  void *stream);
 
+/* Product-quantised codes for the inverted-file index (IVF-PQ; csrc/n2v_ivfpq.hip, DESIGN.md "Product-quantised
+ * codes").  ADDITIONS ONLY: N2V_ABI_VERSION stays 15.  Beside list_off and row_ids (as n2v_ivf_*) the index is
+ * codebooks fp32 [m, 256, dsub], dsub = ceil(dim / m) (the last sub-space padded; dims at or past dim are never
+ * read), and codes uint8 [list_off[nlist], stride], 16-byte aligned, stride = m rounded up to 4, 8, 16, 32 or 64
+ * (plan5[4]); row p of codes belongs to row_ids[p], bytes m .. stride are not looked at.  1 <= m <= min(dim, 64).
+ * X is read only for a query given as a row (query_rows; X and inv_norm may be NULL with queries).  The arithmetic,
+ * fp32, every product and sum rounded once, in an order no tile, chunk or launch size enters:
+ *   lut[q][j][c] = ((+0 + q_hat[j dsub] w_j[c][0]) + q_hat[j dsub + 1] w_j[c][1]) + .., t ascending, j dsub + t < dim,
+ *                  q_hat as n2v_knn_* build it;
+ *   score(q, position p in the list of probe ordinal o) = ((coarse[q][o] + lut[q][0][codes[p][0]]) +
+ *                  lut[q][1][codes[p][1]]) + .., j ascending.
+ * coarse: fp32 [n_queries, nprobe], the first term of every probe (the query's score against that list's centroid).
+ * out_rows / out_scores [n_queries, k]: the k best positions of the probed lists as ORIGINAL row numbers, by score
+ * descending, then row number ascending; a NaN score (a NaN coarse score, a NaN table entry) is never selected;
+ * the tail is row -1, score -inf.  Bounds and status as n2v_ivf_topk: 1 <= k <= 128, argument errors N2V_EINVAL
+ * before any launch, n == 0 or n_queries == 0 N2V_OK without a launch; a list longer than max_list_rows, offsets
+ * that descend, a probe outside [-1, nlist) or a row id outside [0, n) sets N2V_ST_RANGE in status[0]: the call
+ * still runs, reads nothing out of bounds, and its results must be discarded. */
+
+/* Bytes of workspace n2v_ivfpq_topk needs (q_hat, fp32 [n_queries, m, 256] tables, the grouping tables, the slots);
+ * -1 for sizes it refuses (also: more scan blocks than one launch takes -- split the queries), 0 for n == 0 or
+ * n_queries == 0.  k == 0: the workspace of n2v_ivfpq_lut (q_hat alone; n, nlist, max_list_rows and nprobe are not
+ * looked at). */
+int64_t n2v_ivfpq_workspace_bytes(int64_t n, int32_t dim, int32_t m, int32_t nlist, int64_t max_list_rows,
+                                  int64_t n_queries, int32_t nprobe, int32_t k);
+/* The launch shape (host memory): plan5 = {(query, probe) pairs per tile T: 16 (m <= 7), 8 (m <= 16), 4 (m <= 32)
+ * or 2, positions per chunk of a list: a multiple of 128, chunks per list = ceil(max_list_rows / positions per
+ * chunk), bytes of LDS of a scan block (<= 160 KiB), bytes from one row of codes to the next}. */
+int n2v_ivfpq_plan(int64_t n, int32_t dim, int32_t m, int32_t nlist, int64_t max_list_rows, int64_t n_queries,
+                   int32_t nprobe, int32_t k, int64_t *plan5);
+/* lut_out fp32 [n_queries, m, 256], the tables n2v_ivfpq_topk sums from.  workspace: 16-byte aligned, at least
+ * n2v_ivfpq_workspace_bytes(.., k = 0). */
+int n2v_ivfpq_lut(const float *X, const float *inv_norm, int64_t n, int32_t dim, const float *queries,
+                  const int64_t *query_rows, int64_t n_queries, const float *codebooks, int32_t m, float *lut_out,
+                  void *workspace, int64_t workspace_bytes, void *stream);
+/* workspace: 16-byte aligned, workspace_bytes >= n2v_ivfpq_workspace_bytes. */
+int n2v_ivfpq_topk(const uint8_t *codes, const float *codebooks, int32_t m, const float *X, const float *inv_norm,
+                   int64_t n, int32_t dim, const int64_t *list_off, const int32_t *row_ids, int32_t nlist,
+                   int64_t max_list_rows, const float *queries, const int64_t *query_rows, int64_t n_queries,
+                   const int32_t *probes, const float *coarse, int32_t nprobe, int32_t k, int64_t *out_rows,
+                   float *out_scores, uint32_t *status, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Silhouette coefficients of a clustering of trained vectors (csrc/n2v_silhouette.hip, DESIGN.md "Cluster
  * quality").  ADDITIONS ONLY: N2V_ABI_VERSION stays 15.  X, inv_norm, labels, k and metric as for n2v_kmeans_*
  * (metric: N2V_KMEANS_EUCLIDEAN, the true distance sqrt(max(|x_i|^2 + |x_j|^2 - 2 dot, 0)), or N2V_KMEANS_COSINE,

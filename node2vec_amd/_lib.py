@@ -39,7 +39,8 @@ SYMBOLS = ("n2v_abi_version", "n2v_status_string", "n2v_device_count", "n2v_alia
            "n2v_logreg_workspace_bytes", "n2v_logreg_scores", "n2v_logreg_loss_grad", "n2v_pca_slab_rows",
            "n2v_pca_workspace_bytes", "n2v_pca_mean", "n2v_pca_scatter", "n2v_ivf_workspace_bytes", "n2v_ivf_plan",
            "n2v_ivf_topk", "n2v_silhouette_workspace_bytes", "n2v_silhouette", "n2v_tsne_plan",
-           "n2v_tsne_workspace_bytes", "n2v_tsne_repulse", "n2v_tsne_step")
+           "n2v_tsne_workspace_bytes", "n2v_tsne_repulse", "n2v_tsne_step", "n2v_ivfpq_workspace_bytes",
+           "n2v_ivfpq_plan", "n2v_ivfpq_lut", "n2v_ivfpq_topk")
 
 
 class WeightedHubs(C.Structure):
@@ -314,6 +315,19 @@ def load():
     L.n2v_tsne_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p]
+    L.n2v_ivfpq_workspace_bytes.restype = C.c_int64
+    L.n2v_ivfpq_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                                            C.c_int32]
+    L.n2v_ivfpq_plan.restype = C.c_int
+    L.n2v_ivfpq_plan.argtypes = L.n2v_ivfpq_workspace_bytes.argtypes + [C.POINTER(C.c_int64)]
+    L.n2v_ivfpq_lut.restype = C.c_int
+    L.n2v_ivfpq_lut.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.n2v_ivfpq_topk.restype = C.c_int
+    L.n2v_ivfpq_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                 C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                 C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_int64, C.c_void_p]
     _lib = L
     return L
 

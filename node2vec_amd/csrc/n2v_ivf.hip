@@ -11,22 +11,20 @@
 // The index is list_off [nlist + 1] and row_ids (the rows of X in list order); X is read in place through row_ids,
 // whole rows at a time.  One launch sequence, no device-to-host read:
 //   1. q_hat of every query; the partial lists emptied; the lists' lengths checked against max_list_rows
-//   2. the (query, probe) pairs grouped by list: count (integer atomics), scan, fill -- the order inside a group is
-//      whatever the atomics give, and no result depends on it
+//   2. the (query, probe) pairs grouped by list (n2v_ivf_group.h, shared with n2v_ivfpq.hip): count (integer
+//      atomics), scan, fill -- the order inside a group is whatever the atomics give, and no result depends on it
 //   3. block (x = tile of qt pairs of one list, y = chunk of chunk_rows rows of that list): 16 rows x 16 G pairs per
 //      wave step, the candidates in LDS, the sorted k best to the slot (pair, chunk); the grid is sized from an
 //      upper bound on the tiles and the blocks past the real count exit
 //   4. per query the nprobe x chunks slots merged pairwise (merge_kernel)
 // There are no float atomics.
-#include "n2v_topk_select.h"
+#include "n2v_ivf_group.h"
 
 namespace {
 
-constexpr int kMaxLists = 1024;  // cluster.MAX_K
 constexpr int kMaxK = 128;       // k <= CAP - kStepRows
 constexpr int kCap = 256;        // candidates per pair in LDS
 constexpr int kChunkSteps = 16;  // block steps per chunk of a list, about
-constexpr int64_t kMaxBlocks = (int64_t)1 << 22;  // blocks of the scan launch at most (512 threads each)
 
 // the launch shape and the workspace `ws` laid out (ws null: only the sizes mean anything): q_hat, the grouping
 // tables, the pair list, then the two halves (scores, rows) of the slots that the merge ping-pongs
@@ -37,7 +35,8 @@ struct IvfPlan {
   int64_t chunk_rows;  // a multiple of kStepRows
   int64_t pairs, tiles_max, bytes;
   float *qhat, *s0, *s1;
-  int32_t *cnt, *cursor, *pair_off, *tile_off, *pair_list, *r0, *r1;
+  IvfGroups g;
+  int32_t *r0, *r1;
 };
 
 bool sizes_ok(int64_t n, int32_t dim, int32_t nlist, int64_t max_list_rows, int64_t nq, int32_t nprobe, int32_t k) {
@@ -64,92 +63,13 @@ IvfPlan plan_ivf(int64_t n, int32_t dim, int32_t nlist, int64_t max_list_rows, i
   const int64_t part = p.pairs * p.chunks * k * 4;
   Carver carve(ws);
   p.qhat = take_qhat(carve, dim, nq);
-  p.cnt = carve.take<int32_t>(nlist * 4);
-  p.cursor = carve.take<int32_t>(nlist * 4);
-  p.pair_off = carve.take<int32_t>((nlist + 1) * 4);
-  p.tile_off = carve.take<int32_t>((nlist + 1) * 4);
-  p.pair_list = carve.take<int32_t>(p.pairs * 4);
+  p.g = take_groups(carve, nlist, p.pairs);
   p.s0 = carve.take<float>(part);
   p.r0 = carve.take<int32_t>(part);
   p.s1 = carve.take<float>(part);
   p.r1 = carve.take<int32_t>(part);
   p.bytes = carve.used;
   return p;
-}
-
-// every slot empty, the groups' counters zero, and the lists' bounds checked: offsets that descend or a list longer
-// than max_list_rows set N2V_ST_RANGE (the scan clamps what it reads)
-__global__ __launch_bounds__(256) void ivf_prepare_kernel(const int64_t *__restrict__ list_off, int32_t nlist,
-                                                          int64_t max_list_rows, int64_t n_entries,
-                                                          float *__restrict__ part_s, int32_t *__restrict__ part_r,
-                                                          int32_t *__restrict__ cnt, int32_t *__restrict__ cursor,
-                                                          uint32_t *__restrict__ status) {
-  const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
-  for (int64_t i = i0; i < n_entries; i += stride) {
-    part_s[i] = -INFINITY;
-    part_r[i] = kSentinelRow;
-  }
-  for (int64_t l = i0; l < nlist; l += stride) {
-    cnt[l] = 0;
-    cursor[l] = 0;
-    const int64_t a = list_off[l], b = list_off[l + 1];
-    if (a < 0 || b < a || b - a > max_list_rows) atomicOr(status, N2V_ST_RANGE);
-  }
-}
-
-// a probe is a list number, or -1 for an unused slot; anything else sets N2V_ST_RANGE and is skipped
-__device__ inline bool probe_ok(int32_t l, int32_t nlist, uint32_t *status) {
-  if (l >= 0 && l < nlist) return true;
-  if (l != -1) atomicOr(status, N2V_ST_RANGE);
-  return false;
-}
-
-__global__ __launch_bounds__(256) void ivf_count_kernel(const int32_t *__restrict__ probes, int64_t pairs,
-                                                        int32_t nlist, int32_t *__restrict__ cnt,
-                                                        uint32_t *__restrict__ status) {
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < pairs; i += stride) {
-    const int32_t l = probes[i];
-    if (probe_ok(l, nlist, status)) atomicAdd(&cnt[l], 1);
-  }
-}
-
-// pair_off / tile_off: the exclusive sums over the lists of the pairs and of the tiles of qt pairs; one block
-__global__ __launch_bounds__(kMaxLists) void ivf_scan_kernel(const int32_t *__restrict__ cnt, int32_t nlist, int32_t qt,
-                                                             int32_t *__restrict__ pair_off,
-                                                             int32_t *__restrict__ tile_off) {
-  __shared__ int32_t sp[kMaxLists], st[kMaxLists];
-  const int i = threadIdx.x;
-  const int32_t c = i < nlist ? cnt[i] : 0;
-  int32_t p = c, t = (c + qt - 1) / qt;
-  sp[i] = p;
-  st[i] = t;
-  __syncthreads();
-  for (int off = 1; off < kMaxLists; off <<= 1) {
-    const int32_t ap = i >= off ? sp[i - off] : 0, at = i >= off ? st[i - off] : 0;
-    __syncthreads();
-    p += ap;
-    t += at;
-    sp[i] = p;
-    st[i] = t;
-    __syncthreads();
-  }
-  if (i == 0) pair_off[0] = tile_off[0] = 0;
-  if (i < nlist) {
-    pair_off[i + 1] = p;
-    tile_off[i + 1] = t;
-  }
-}
-
-__global__ __launch_bounds__(256) void ivf_group_kernel(const int32_t *__restrict__ probes, int64_t pairs,
-                                                        int32_t nlist, const int32_t *__restrict__ pair_off,
-                                                        int32_t *__restrict__ cursor,
-                                                        int32_t *__restrict__ pair_list) {
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < pairs; i += stride) {
-    const int32_t l = probes[i];
-    if (l >= 0 && l < nlist) pair_list[pair_off[l] + atomicAdd(&cursor[l], 1)] = (int32_t)i;
-  }
 }
 
 // Block (x = tile, y = chunk): the tile's list is found in tile_off, its pairs in pair_list; the chunk's rows are
@@ -169,12 +89,7 @@ __global__ __launch_bounds__(kWaves * 64) void ivf_topk_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int32_t tile = blockIdx.x, chunk = blockIdx.y;
   if (tile >= tile_off[nlist]) return;
-  int32_t l = 0, above = nlist;  // tile_off[l] <= tile < tile_off[above]
-  while (above - l > 1) {
-    const int32_t m = (l + above) >> 1;
-    if (tile_off[m] <= tile) l = m;
-    else above = m;
-  }
+  const int32_t l = list_of_tile(tile_off, nlist, tile);
   const int64_t begin = list_off[l];
   int64_t len = list_off[l + 1] - begin;
   if (len > max_list_rows) len = max_list_rows;
@@ -236,13 +151,8 @@ void launch_scan(const IvfPlan &p, const float *X, const float *inv_norm, int64_
   with_bool(vec_ok(dim, X), [&](auto VEC) {
     hipLaunchKernelGGL((ivf_topk_kernel<G, QACT, VEC>), grid, dim3(kWaves * 64), 0, st, X, inv_norm, n, dim, list_off,
                        row_ids, nlist, max_list_rows, p.qhat, nq_pad_of(nq) - 1, nprobe, k, p.chunk_rows, p.chunks,
-                       p.pair_off, p.tile_off, p.pair_list, p.s0, p.r0, status);
+                       p.g.pair_off, p.g.tile_off, p.g.pair_list, p.s0, p.r0, status);
   });
-}
-
-unsigned blocks_for(int64_t items) {
-  const int64_t b = (items + 255) / 256;
-  return (unsigned)(b < 1 ? 1 : b > 65536 ? 65536 : b);
 }
 
 }  // namespace
@@ -282,18 +192,9 @@ int n2v_ivf_topk(const float *X, const float *inv_norm, int64_t n, int32_t dim, 
   hipStream_t st = (hipStream_t)stream;
   const int rc = launch_queries(X, inv_norm, dim, queries, query_rows, n_queries, p.qhat, st);
   if (rc != N2V_OK) return rc;
-  const int64_t entries = p.pairs * p.chunks * k;
-  hipLaunchKernelGGL(ivf_prepare_kernel, dim3(blocks_for(entries)), dim3(256), 0, st, list_off, nlist, max_list_rows,
-                     entries, p.s0, p.r0, p.cnt, p.cursor, status);
-  N2V_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(ivf_count_kernel, dim3(blocks_for(p.pairs)), dim3(256), 0, st, probes, p.pairs, nlist, p.cnt,
-                     status);
-  N2V_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), dim3(kMaxLists), 0, st, p.cnt, nlist, p.qt, p.pair_off, p.tile_off);
-  N2V_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(ivf_group_kernel, dim3(blocks_for(p.pairs)), dim3(256), 0, st, probes, p.pairs, nlist, p.pair_off,
-                     p.cursor, p.pair_list);
-  N2V_HIP_CHECK(hipGetLastError());
+  const int rg = launch_groups(p.g, list_off, nlist, max_list_rows, probes, p.pairs, p.qt, p.pairs * p.chunks * k, p.s0,
+                              p.r0, status, st);
+  if (rg != N2V_OK) return rg;
   if (p.qt == 64)
     launch_scan<4, 64>(p, X, inv_norm, n, dim, list_off, row_ids, nlist, max_list_rows, n_queries, nprobe, k, status, st);
   else

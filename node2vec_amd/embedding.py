@@ -246,16 +246,36 @@ class KeyedVectors:
         query = mean / norm if norm > 0 else mean
         return query.astype(np.float32), sorted({row for row, _, _ in parsed if row is not None})
 
-    def build_index(self, nlist: Optional[int] = None, nprobe: int = 8, seed: int = 0, **kw):
+    def build_index(self, nlist: Optional[int] = None, nprobe: int = 8, seed: int = 0, pq: Optional[int] = None,
+                    refine: int = 4, **kw):
         """An inverted-file index over the vectors for approximate queries (node2vec_amd.ann.build_index, whose other
         arguments pass through): spherical k-means into nlist lists over the cached init_sims norms.  Hand it to
         most_similar / similar_by_* / nearest as indexer=; its nprobe (lists scanned per query) may be set at any
-        time.  It indexes the vectors as they are now."""
+        time.  It indexes the vectors as they are now.  pq=m: an IVFPQIndex (ann.build_pq: m bytes per vector,
+        trained with the same seed), searched by ann.search_pq -- approximate scores over the codes, the best
+        refine * topn of them scored exactly again (index.refine, settable; 0: the approximate scores as they
+        are)."""
         from node2vec_amd import ann
 
         self.init_sims()
-        return ann.build_index(self._device_vectors(), nlist=nlist, nprobe=nprobe, seed=seed,
-                               inv_norm=self._inv_norm, **kw)
+        X = self._device_vectors()
+        index = ann.build_index(X, nlist=nlist, nprobe=nprobe, seed=seed, inv_norm=self._inv_norm, **kw)
+        if pq is None:
+            return index
+        if int(refine) < 0:
+            raise ValueError("refine must be >= 0")
+        index = ann.build_pq(X, index, pq, seed=seed, inv_norm=self._inv_norm)
+        index.refine = int(refine)
+        return index
+
+    def _index_search(self, indexer, k: int, **kw):
+        """ann.search, or ann.search_pq for an index with product-quantised codes"""
+        from node2vec_amd import ann
+
+        X = self._device_vectors()
+        if isinstance(indexer, ann.IVFPQIndex):
+            return ann.search_pq(indexer, k, X=X, refine=indexer.refine, inv_norm=self._inv_norm, **kw)
+        return ann.search(X, indexer, k, inv_norm=self._inv_norm, **kw)
 
     @staticmethod
     def _check_indexer(topn, restrict_vocab) -> None:
@@ -287,9 +307,7 @@ class KeyedVectors:
         if topn is None:
             return similarity.scores(X, queries=q, restrict=restrict_vocab, inv_norm=self._inv_norm)[0].cpu().numpy()
         if indexer is not None:
-            from node2vec_amd import ann
-
-            rows, scores = ann.search(X, indexer, int(topn) + len(own), queries=q, inv_norm=self._inv_norm)
+            rows, scores = self._index_search(indexer, int(topn) + len(own), queries=q)
         else:
             rows, scores = similarity.knn(X, int(topn) + len(own), queries=q, restrict=restrict_vocab,
                                           inv_norm=self._inv_norm)
@@ -322,10 +340,7 @@ class KeyedVectors:
             self._check_indexer(topn, restrict_vocab)
         self.init_sims()
         if indexer is not None:
-            from node2vec_amd import ann
-
-            return ann.search(self._device_vectors(), indexer, topn, rows=rows, inv_norm=self._inv_norm,
-                              exclude_self=exclude_self)
+            return self._index_search(indexer, topn, rows=rows, exclude_self=exclude_self)
         return similarity.knn(self._device_vectors(), topn, rows=rows, restrict=restrict_vocab,
                               inv_norm=self._inv_norm, exclude_self=exclude_self)
 
