@@ -111,21 +111,6 @@ def _nprobe(index: IVFIndex, nprobe) -> int:
     return min(nprobe, index.nlist)
 
 
-def _query_vectors(index, queries, rows, X):
-    """unit-free query vectors [nq, dim] for the centroid search (knn normalises them itself)"""
-    if (queries is None) == (rows is None):
-        raise ValueError("give exactly one of queries= / rows=")
-    if rows is not None:
-        if X is None:
-            raise ValueError("rows= needs X")
-        rows = torch.as_tensor(rows, device=X.device).to(torch.int64).reshape(-1)
-        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= X.shape[0]):
-            raise IndexError("query row outside [0, n)")
-        return X[rows].contiguous()
-    queries = torch.as_tensor(queries, device=index.centroids.device)
-    return queries[None] if queries.ndim == 1 else queries
-
-
 def probe(index: IVFIndex, queries=None, rows=None, X: Optional[torch.Tensor] = None,
           inv_norm: Optional[torch.Tensor] = None, nprobe: Optional[int] = None) -> torch.Tensor:
     """int32 [nq, nprobe]: for every query the nprobe lists whose centroids are nearest by cosine -- similarity.knn
@@ -133,7 +118,14 @@ def probe(index: IVFIndex, queries=None, rows=None, X: Optional[torch.Tensor] = 
     prefix of those of a larger one.  A query no centroid scores (a NaN query) gets -1.  rows= are rows of X, which
     must then be given; inv_norm is accepted as search() accepts it and not needed: knn normalises the queries."""
     nprobe = _nprobe(index, nprobe)
-    q = _query_vectors(index, queries, rows, X)
+    if (queries is None) == (rows is None):
+        raise ValueError("give exactly one of queries= / rows=")
+    if rows is None:  # the vectors as they are: knn normalises them itself
+        q = _dense.queries(queries, index.centroids.shape[1], index.centroids.device)
+    elif X is None:
+        raise ValueError("rows= needs X")
+    else:
+        q = X[_dense.rows(rows, X.shape[0], X.device)].contiguous()
     lists, _ = similarity.knn(index.centroids, nprobe, queries=q, inv_norm=index.centroid_inv_norm)
     return lists.to(torch.int32)
 
@@ -146,26 +138,33 @@ def plan(n: int, dim: int, nlist: int, max_list_rows: int, n_queries: int, nprob
     return int(out[0]), int(out[1]), int(out[2])
 
 
+def _scan(name, need, launch, nq, k, device, empty):
+    """_dense.topk_batches for the two scans of an index: at most 2^20 - 1 queries a launch, and the status word
+    launch(i, j, ws, out_r, out_s, status) hands to the library, read once after the last launch"""
+    status = []  # made before the first launch: an empty problem has none and reads nothing
+
+    def run(*args):
+        if not status:
+            status.append(torch.zeros(1, dtype=torch.int32, device=device))
+        launch(*args, status[0])
+
+    out = _dense.topk_batches(need, run, nq, k, device, max_step=(1 << 20) - 1, empty=empty)
+    if status and int(status[0]) & _lib.ST_RANGE:
+        raise ValueError(f"{name}: a list longer than max_list_rows, a probe outside [-1, nlist) or a row id "
+                         "outside [0, n): the index does not belong to these arguments")
+    return out
+
+
 def _topk(X, inv_norm, index, queries, rows, probes, k):
     L = _lib.load()
     n, dim = X.shape
     nq, nprobe = probes.shape
-    out_r = torch.full((nq, k), -1, dtype=torch.int64, device=X.device)
-    out_s = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=X.device)
-    if n == 0 or nq == 0:
-        return out_r, out_s
     sizes = (n, dim, index.nlist, index.max_list_rows)
 
     def need(count):
         return int(L.n2v_ivf_workspace_bytes(*sizes, count, nprobe, k))
 
-    step = min(nq, (1 << 20) - 1)  # queries per launch: the workspace stays under WORKSPACE_LIMIT
-    while step > 1 and not 0 <= need(step) <= similarity.WORKSPACE_LIMIT:
-        step = (step + 1) // 2
-    status = torch.zeros(1, dtype=torch.int32, device=X.device)
-    for i in range(0, nq, step):
-        j = min(nq, i + step)
-        ws = _dense.workspace(L.n2v_ivf_workspace_bytes, *sizes, j - i, nprobe, k, device=X.device)
+    def launch(i, j, ws, out_r, out_s, status):
         q = None if queries is None else queries[i:j]
         r = None if rows is None else rows[i:j]
         _lib.check(L.n2v_ivf_topk(X.data_ptr(), inv_norm.data_ptr(), n, dim, index.list_off.data_ptr(),
@@ -173,10 +172,48 @@ def _topk(X, inv_norm, index, queries, rows, probes, k):
                                   _dense.ptr(r), j - i, probes[i:j].data_ptr(), nprobe, k, out_r[i:j].data_ptr(),
                                   out_s[i:j].data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
                                   _lib.current_stream_ptr()), "n2v_ivf_topk")
-    if int(status) & _lib.ST_RANGE:
-        raise ValueError("n2v_ivf_topk: a list longer than max_list_rows, a probe outside [-1, nlist) or a row id "
-                         "outside [0, n): the index does not belong to these arguments")
-    return out_r, out_s
+
+    return _scan("n2v_ivf_topk", need, launch, nq, k, X.device, n == 0)
+
+
+def _front(kind, index, k, refine, queries, rows, X, inv_norm, probes, exclude_self):
+    """What search (kind IVFIndex) and search_pq (kind IVFPQIndex) check before they scan, in the order they
+    promise their errors in: (k, k + exclude_self, X, inv_norm, queries, rows, probes), the last three as the
+    library takes them (probes None: the caller finds them).  Only search_pq may go without X."""
+    k, refine, pq = int(k), int(refine), kind is IVFPQIndex
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    if refine < 0:
+        raise ValueError("refine must be >= 0")
+    if exclude_self and rows is None:
+        raise ValueError("exclude_self needs rows=")
+    want = k + 1 if exclude_self else k
+    if want > MAX_K:
+        raise ValueError(f"k = {k}{' + 1 (exclude_self)' if exclude_self else ''} is above the index's limit of "
+                         f"{MAX_K}: similarity.knn serves larger k exactly")
+    if not isinstance(index, kind):
+        raise ValueError(f"index must be an {kind.__name__} (ann.{'build_pq' if pq else 'build_index'})")
+    if pq:
+        if (queries is None) == (rows is None):
+            raise ValueError("give exactly one of queries= / rows=")
+        if X is None and rows is not None:
+            raise ValueError("rows= needs X")
+        if X is None and refine > 0:
+            raise ValueError("refine > 0 needs X: the exact scores are computed from its rows")
+    if X is not None or not pq:
+        n, dim = _dense.shape(X)
+        if (n, dim) != (index.n, index.dim):
+            raise ValueError(f"the index was built on a [{index.n}, {index.dim}] matrix, not [{n}, {dim}]")
+        X, inv_norm, queries, rows = similarity._inputs(X, queries, rows, None, inv_norm)
+    else:
+        queries, rows, inv_norm = _dense.queries(queries, index.dim, index.codes.device), None, None
+    if probes is not None:
+        nq = (rows if rows is not None else queries).shape[0]
+        probes = torch.as_tensor(probes, device=index.codes.device if pq else X.device)
+        if probes.ndim != 2 or probes.shape[0] != nq or not 1 <= probes.shape[1] <= index.nlist:
+            raise ValueError(f"probes must be [{nq}, 1 .. {index.nlist}]")
+        probes = probes.to(torch.int32).contiguous()
+    return k, want, X, inv_norm, queries, rows, probes
 
 
 def search(X: torch.Tensor, index: IVFIndex, k: int, queries=None, rows=None, nprobe: Optional[int] = None,
@@ -187,37 +224,13 @@ def search(X: torch.Tensor, index: IVFIndex, k: int, queries=None, rows=None, np
     score is never selected.  X: the matrix the index was built on.  nprobe: lists per query (default: the index's);
     probes: int32 [nq, nprobe'] of list numbers (-1: unused, a query's entries distinct) instead of probe()'s.
     exclude_self (rows= only): a query's own row is not returned (k + 1 are asked for).  k + exclude_self <= 128."""
-    k = int(k)
-    if k < 1:
-        raise ValueError("k must be >= 1")
-    if exclude_self and rows is None:
-        raise ValueError("exclude_self needs rows=")
-    want = k + 1 if exclude_self else k
-    if want > MAX_K:
-        raise ValueError(f"k = {k}{' + 1 (exclude_self)' if exclude_self else ''} is above the index's limit of "
-                         f"{MAX_K}: similarity.knn serves larger k exactly")
-    if not isinstance(index, IVFIndex):
-        raise ValueError("index must be an IVFIndex (ann.build_index)")
-    n, dim = _dense.shape(X)
-    if (n, dim) != (index.n, index.dim):
-        raise ValueError(f"the index was built on a [{index.n}, {index.dim}] matrix, not [{n}, {dim}]")
-    X, inv_norm, queries, qrows = similarity._inputs(X, queries, rows, None, inv_norm)
-    nq = (qrows if qrows is not None else queries).shape[0]
+    k, want, X, inv_norm, queries, qrows, probes = _front(IVFIndex, index, k, 0, queries, rows, X, inv_norm, probes,
+                                                          exclude_self)
     with torch.cuda.device(X.device):
         if probes is None:
             probes = probe(index, queries=queries, rows=qrows, X=X, nprobe=nprobe)
-        else:
-            probes = torch.as_tensor(probes, device=X.device)
-            if probes.ndim != 2 or probes.shape[0] != nq or not 1 <= probes.shape[1] <= index.nlist:
-                raise ValueError(f"probes must be [{nq}, 1 .. {index.nlist}]")
-        probes = probes.to(torch.int32).contiguous()
         out_r, out_s = _topk(X, inv_norm, index, queries, qrows, probes, want)
-    if not exclude_self:
-        return out_r, out_s
-    drop = out_r == qrows[:, None]
-    drop[:, -1] |= ~drop.any(dim=1)  # not among the k + 1: the last one goes
-    keep = ~drop
-    return out_r[keep].view(-1, k), out_s[keep].view(-1, k)
+    return _dense.drop_self(out_r, out_s, qrows, k) if exclude_self else (out_r, out_s)
 
 
 # ---- product-quantised codes (IVF-PQ) -------------------------------------------------------------------------------
@@ -273,12 +286,7 @@ def _pq_inputs(X, index, m, inv_norm):
         raise ValueError("index must be an IVFIndex (ann.build_index)")
     if (n, dim) != (index.n, index.dim):
         raise ValueError(f"the index was built on a [{index.n}, {index.dim}] matrix, not [{n}, {dim}]")
-    m = _check_m(m, dim)
-    if inv_norm is None:
-        inv_norm = similarity.inv_norms(X)
-    elif inv_norm.ndim != 1 or inv_norm.shape[0] < n:
-        raise ValueError("inv_norm must hold one value per row of X")
-    return X, m, inv_norm[:n].to(device=X.device, dtype=torch.float32)
+    return X, _check_m(m, dim), _dense.norms(X, inv_norm)
 
 
 def pq_train(X: torch.Tensor, index: IVFIndex, m: int, seed: int = 0, train_rows: Optional[int] = None,
@@ -376,10 +384,7 @@ def pq_lut(codebooks: torch.Tensor, dim: int, queries=None, rows=None, X: Option
         X, inv_norm, _, rows = similarity._inputs(X, None, rows, None, inv_norm)
         n = X.shape[0]
     else:
-        queries = torch.as_tensor(queries, device=codebooks.device).to(torch.float32)
-        queries = (queries[None] if queries.ndim == 1 else queries).contiguous()
-        if queries.ndim != 2 or queries.shape[1] != dim:
-            raise ValueError(f"queries must be [n_queries, {dim}]")
+        queries = _dense.queries(queries, dim, codebooks.device)
     nq = (rows if rows is not None else queries).shape[0]
     out = torch.empty((nq, m, PQ_CODEWORDS), dtype=torch.float32, device=codebooks.device)
     if nq == 0:
@@ -396,23 +401,12 @@ def pq_lut(codebooks: torch.Tensor, dim: int, queries=None, rows=None, X: Option
 def _pq_topk(index: IVFPQIndex, X, inv_norm, queries, rows, probes, coarse, k):
     L = _lib.load()
     nq, nprobe = probes.shape
-    dev = index.codes.device
-    out_r = torch.full((nq, k), -1, dtype=torch.int64, device=dev)
-    out_s = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev)
-    if index.n == 0 or nq == 0 or index.codes.shape[0] == 0:
-        return out_r, out_s
     sizes = (index.n, index.dim, index.m, index.nlist, index.max_list_rows)
 
     def need(count):
         return int(L.n2v_ivfpq_workspace_bytes(*sizes, count, nprobe, k))
 
-    step = min(nq, (1 << 20) - 1)  # queries per launch: the workspace stays under WORKSPACE_LIMIT
-    while step > 1 and not 0 <= need(step) <= similarity.WORKSPACE_LIMIT:
-        step = (step + 1) // 2
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    for i in range(0, nq, step):
-        j = min(nq, i + step)
-        ws = _dense.workspace(L.n2v_ivfpq_workspace_bytes, *sizes, j - i, nprobe, k, device=dev)
+    def launch(i, j, ws, out_r, out_s, status):
         q = None if queries is None else queries[i:j]
         r = None if rows is None else rows[i:j]
         _lib.check(L.n2v_ivfpq_topk(index.codes.data_ptr(), index.codebooks.data_ptr(), index.m, _dense.ptr(X),
@@ -421,10 +415,9 @@ def _pq_topk(index: IVFPQIndex, X, inv_norm, queries, rows, probes, coarse, k):
                                     _dense.ptr(r), j - i, probes[i:j].data_ptr(), coarse[i:j].data_ptr(), nprobe, k,
                                     out_r[i:j].data_ptr(), out_s[i:j].data_ptr(), status.data_ptr(), ws.data_ptr(),
                                     ws.numel(), _lib.current_stream_ptr()), "n2v_ivfpq_topk")
-    if int(status) & _lib.ST_RANGE:
-        raise ValueError("n2v_ivfpq_topk: a list longer than max_list_rows, a probe outside [-1, nlist) or a row id "
-                         "outside [0, n): the index does not belong to these arguments")
-    return out_r, out_s
+
+    return _scan("n2v_ivfpq_topk", need, launch, nq, k, index.codes.device,
+                 index.n == 0 or index.codes.shape[0] == 0)
 
 
 def _rerank(X, inv_norm, queries, rows, cand: torch.Tensor, k: int):
@@ -462,60 +455,22 @@ def search_pq(index: IVFPQIndex, k: int, queries=None, rows=None, X: Optional[to
     again with similarity.knn's scores, bit for bit, and the k best by (exact score descending, row ascending)
     returned -- a NaN score is dropped there.  exclude_self (rows= only): a query's own row is not returned.
     k + exclude_self <= 128."""
-    k = int(k)
+    k, want, X, inv_norm, queries, qrows, probes = _front(IVFPQIndex, index, k, refine, queries, rows, X, inv_norm,
+                                                          probes, exclude_self)
     refine = int(refine)
-    if k < 1:
-        raise ValueError("k must be >= 1")
-    if refine < 0:
-        raise ValueError("refine must be >= 0")
-    if exclude_self and rows is None:
-        raise ValueError("exclude_self needs rows=")
-    want = k + 1 if exclude_self else k
-    if want > MAX_K:
-        raise ValueError(f"k = {k}{' + 1 (exclude_self)' if exclude_self else ''} is above the index's limit of "
-                         f"{MAX_K}: similarity.knn serves larger k exactly")
-    if not isinstance(index, IVFPQIndex):
-        raise ValueError("index must be an IVFPQIndex (ann.build_pq)")
-    if (queries is None) == (rows is None):
-        raise ValueError("give exactly one of queries= / rows=")
-    if X is None and rows is not None:
-        raise ValueError("rows= needs X")
-    if X is None and refine > 0:
-        raise ValueError("refine > 0 needs X: the exact scores are computed from its rows")
-    qrows = None
-    if X is not None:
-        n, dim = _dense.shape(X)
-        if (n, dim) != (index.n, index.dim):
-            raise ValueError(f"the index was built on a [{index.n}, {index.dim}] matrix, not [{n}, {dim}]")
-        X, inv_norm, queries, qrows = similarity._inputs(X, queries, rows, None, inv_norm)
-    else:
-        queries = torch.as_tensor(queries, device=index.codes.device)
-        queries = (queries[None] if queries.ndim == 1 else queries).to(torch.float32).contiguous()
-        if queries.ndim != 2 or queries.shape[1] != index.dim:
-            raise ValueError(f"queries must be [n_queries, {index.dim}]")
-        inv_norm = None
-    nq = (qrows if qrows is not None else queries).shape[0]
     with torch.cuda.device(index.codes.device):
         qvec = queries if qrows is None else X[qrows].contiguous()
         if probes is None:
             probes, coarse = similarity.knn(index.centroids, _nprobe(index, nprobe), queries=qvec,
                                             inv_norm=index.centroid_inv_norm)
+            probes = probes.to(torch.int32)
         else:
-            probes = torch.as_tensor(probes, device=index.codes.device)
-            if probes.ndim != 2 or probes.shape[0] != nq or not 1 <= probes.shape[1] <= index.nlist:
-                raise ValueError(f"probes must be [{nq}, 1 .. {index.nlist}]")
             every = similarity.scores(index.centroids, queries=qvec, inv_norm=index.centroid_inv_norm)
             coarse = torch.gather(every, 1, probes.long().clamp(0, index.nlist - 1))
-        probes = probes.to(torch.int32).contiguous()
         coarse = coarse.to(torch.float32).contiguous()
         first = want if refine == 0 else min(MAX_K, max(want, refine * want))
         out_r, out_s = _pq_topk(index, X if qrows is not None else None, inv_norm if qrows is not None else None,
                                 queries, qrows, probes, coarse, first)
         if refine > 0:
             out_r, out_s = _rerank(X, inv_norm, queries, qrows, out_r, want)
-    if not exclude_self:
-        return out_r, out_s
-    drop = out_r == qrows[:, None]
-    drop[:, -1] |= ~drop.any(dim=1)  # not among the k + 1: the last one goes
-    keep = ~drop
-    return out_r[keep].view(-1, k), out_s[keep].view(-1, k)
+    return _dense.drop_self(out_r, out_s, qrows, k) if exclude_self else (out_r, out_s)

@@ -61,13 +61,7 @@ def check_k(k, n: Optional[int] = None) -> int:
 
 
 def _norms(X: torch.Tensor, metric: str, inv_norm: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    if metric != "cosine":
-        return None
-    if inv_norm is None:
-        return similarity.inv_norms(X)
-    if inv_norm.ndim != 1 or inv_norm.shape[0] < X.shape[0]:
-        raise ValueError("inv_norm must hold one value per row of X")
-    return inv_norm[:X.shape[0]].to(device=X.device, dtype=torch.float32).contiguous()
+    return _dense.norms(X, inv_norm) if metric == "cosine" else None
 
 
 def _centroids(C, k: Optional[int], dim: int) -> torch.Tensor:

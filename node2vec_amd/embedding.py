@@ -391,17 +391,8 @@ class KeyedVectors:
         from node2vec_amd import cluster
 
         cluster.check_metric(metric)
-        n = len(self)
-        if restrict_vocab is not None:
-            if int(restrict_vocab) < 0:
-                raise ValueError("restrict_vocab must be >= 0")
-            n = min(n, int(restrict_vocab))
-        cluster.check_k(k, n)
-        X = self._device_vectors()[:n]
-        inv_norm = None
-        if metric == "cosine":
-            self.init_sims()
-            inv_norm = self._inv_norm[:n]
+        cluster.check_k(k, self._first_rows(restrict_vocab))
+        X, inv_norm = self._window(restrict_vocab, metric == "cosine")
         return cluster.kmeans(X, k, metric=metric, inv_norm=inv_norm, **kw)
 
     def silhouette(self, labels_or_result, metric: str = "cosine", restrict_vocab: Optional[int] = None, **kw):
@@ -412,13 +403,8 @@ class KeyedVectors:
         from node2vec_amd import cluster
 
         cluster.check_metric(metric)
-        n = self._first_rows(restrict_vocab)
-        inv_norm = None
-        if metric == "cosine":
-            self.init_sims()
-            inv_norm = self._inv_norm[:n]
-        return cluster.silhouette_samples(self._device_vectors()[:n], labels_or_result, metric=metric,
-                                          inv_norm=inv_norm, **kw)
+        X, inv_norm = self._window(restrict_vocab, metric == "cosine")
+        return cluster.silhouette_samples(X, labels_or_result, metric=metric, inv_norm=inv_norm, **kw)
 
     def logreg(self, Y, restrict_vocab: Optional[int] = None, **kw):
         """one-vs-rest logistic regression of the vectors on the GPU (node2vec_amd.classify.fit, whose other
@@ -426,15 +412,11 @@ class KeyedVectors:
         index2word[i].  restrict_vocab: only the first rows are used."""
         from node2vec_amd import classify
 
-        n = len(self)
-        if restrict_vocab is not None:
-            if int(restrict_vocab) < 0:
-                raise ValueError("restrict_vocab must be >= 0")
-            n = min(n, int(restrict_vocab))
+        n = self._first_rows(restrict_vocab)
         Y = torch.as_tensor(Y)
         if Y.ndim != 2 or Y.shape[0] < n:
             raise ValueError(f"Y must hold one row of labels per vector: [{n}, c]")
-        return classify.fit(self._device_vectors()[:n], Y[:n], **kw)
+        return classify.fit(self._window(restrict_vocab, False)[0], Y[:n], **kw)
 
     def label_scores(self, result) -> torch.Tensor:
         """fp32 [n, c] on the device: the decision function of a LogRegResult for every vector"""
@@ -450,6 +432,13 @@ class KeyedVectors:
             n = min(n, int(restrict_vocab))
         return n
 
+    def _window(self, restrict_vocab: Optional[int], cosine: bool):
+        """(the first rows of the matrix on the GPU, their cached init_sims norms -- None unless cosine)"""
+        n = self._first_rows(restrict_vocab)
+        if cosine:
+            self.init_sims()
+        return self._device_vectors()[:n], self._inv_norm[:n] if cosine else None
+
     def pca(self, n_components: Optional[int] = 2, metric: str = "cosine", restrict_vocab: Optional[int] = None,
             **kw):
         """principal components of the vectors on the GPU (node2vec_amd.pca.fit, whose other arguments pass
@@ -459,25 +448,18 @@ class KeyedVectors:
         from node2vec_amd import cluster, pca
 
         cluster.check_metric(metric)
-        n = self._first_rows(restrict_vocab)
+        self._first_rows(restrict_vocab)  # its ValueError first, as before
         pca.check_components(n_components, self.vector_size)
-        inv_norm = None
-        if metric == "cosine":
-            self.init_sims()
-            inv_norm = self._inv_norm[:n]
-        return pca.fit(self._device_vectors()[:n], n_components, unit=metric == "cosine", inv_norm=inv_norm, **kw)
+        X, inv_norm = self._window(restrict_vocab, metric == "cosine")
+        return pca.fit(X, n_components, unit=metric == "cosine", inv_norm=inv_norm, **kw)
 
     def project(self, result, restrict_vocab: Optional[int] = None) -> torch.Tensor:
         """fp32 [n, k] on the device: row i is token index2word[i] on the components of a PCAResult
         (node2vec_amd.pca.transform); NaN for a vector that holds a non-finite value"""
         from node2vec_amd import pca
 
-        n = self._first_rows(restrict_vocab)
-        inv_norm = None
-        if result.unit:
-            self.init_sims()
-            inv_norm = self._inv_norm[:n]
-        return pca.transform(self._device_vectors()[:n], result, inv_norm=inv_norm)
+        X, inv_norm = self._window(restrict_vocab, result.unit)
+        return pca.transform(X, result, inv_norm=inv_norm)
 
     def tsne(self, perplexity: float = 30.0, restrict_vocab: Optional[int] = None, **kw):
         """the t-SNE map of the vectors on the GPU (node2vec_amd.tsne.fit, whose other arguments pass through): a
@@ -486,9 +468,8 @@ class KeyedVectors:
         rows."""
         from node2vec_amd import tsne
 
-        n = self._first_rows(restrict_vocab)
-        self.init_sims()
-        return tsne.fit(self._device_vectors()[:n], perplexity=perplexity, inv_norm=self._inv_norm[:n], **kw)
+        X, inv_norm = self._window(restrict_vocab, True)
+        return tsne.fit(X, perplexity=perplexity, inv_norm=inv_norm, **kw)
 
     @classmethod
     def load_word2vec_format(cls, fname: str) -> "KeyedVectors":
@@ -540,15 +521,55 @@ def _check_objective(p: Dict[str, Any]) -> None:
         raise ValueError("batched is a skip-gram trainer: not available with sg=0 (CBOW)")
 
 
-class _PairQueries:
-    """link_scores() / edge_embedding() of a fitted model: what Node2VecHIP and Node2VecSpark share.  `df_edges`
-    holds vertex ids in columns "src" and "dst"; an id outside the vocabulary is a KeyError."""
+class _ModelQueries:
+    """The queries of a fitted model that Node2VecHIP and Node2VecSpark share: link_scores() / edge_embedding(),
+    cluster() / silhouette(), classify(), project() and tsne().  They answer per vertex in vocabulary order, under
+    ["id"], or ["name"] through name_id: a repeated id keeps its last name, and an id of the vocabulary that
+    name_id does not list is a KeyError -- raised before any GPU work."""
 
     model = None
+    name_id = None
+    clusters = None
+    kmeans_result = None
+    silhouette_score = None
+    _cluster_metric = "cosine"
+    classifier = None
+    label_f1 = None
+    pca_result = None
+    tsne_result = None
 
-    def _edge_ids(self, df_edges: pd.DataFrame):
+    def _wv(self) -> KeyedVectors:
         if self.model is None:
             raise ValueError("Model is not available. Please run fit()")
+        return self.model.wv
+
+    @staticmethod
+    def _vocab_ids(wv: KeyedVectors, lo: int = 0, hi: Optional[int] = None) -> np.ndarray:
+        """the vertex ids of rows [lo, hi), int64"""
+        if wv.ids is not None:
+            return wv.ids[lo:hi]
+        return np.array([int(t) for t in wv.index2word[lo:hi]], dtype=np.int64)
+
+    def _names(self) -> Optional[pd.Series]:
+        """name_id as id -> name (embedding.py:139-140 builds a dict: a repeated id keeps its LAST name)"""
+        if self.name_id is None:
+            return None
+        return self.name_id.drop_duplicates("id", keep="last").set_index("id")["name"]
+
+    def _who(self, ids: np.ndarray, names=False):
+        """("id", ids), or ("name", their names); KeyError: the first of `ids` that name_id does not list.
+        names: self._names(), for a caller that asks more than once"""
+        names = self._names() if names is False else names
+        if names is None:
+            return "id", ids
+        missing = ~pd.Index(ids).isin(names.index)
+        if missing.any():
+            raise KeyError(int(np.asarray(ids)[missing][0]))
+        return "name", names.reindex(ids).to_numpy()
+
+    def _edge_ids(self, df_edges: pd.DataFrame):
+        """`df_edges` holds vertex ids in columns "src" and "dst"; an id outside the vocabulary is a KeyError"""
+        self._wv()
         if "src" not in df_edges.columns or "dst" not in df_edges.columns:
             raise ValueError('df_edges must have the columns "src" and "dst"')
         return df_edges["src"].to_numpy(), df_edges["dst"].to_numpy()
@@ -564,39 +585,16 @@ class _PairQueries:
         vectors = corpus.list_column(self.model.wv.edge_features(src, dst, operator))
         return pd.DataFrame({"src": src, "dst": dst, "vector": vectors})
 
-
-class _ClusterQueries:
-    """cluster() of a fitted model: what Node2VecHIP and Node2VecSpark share."""
-
-    model = None
-    name_id = None
-    clusters = None
-    kmeans_result = None
-    silhouette_score = None
-    _cluster_metric = "cosine"
-
     def cluster(self, k: int, metric: str = "cosine", **kw) -> pd.DataFrame:
         """["id" | "name", "cluster"]: the k-means cluster of every vocabulary vertex, in vocabulary order
         (model.wv.kmeans, whose other arguments pass through; -1: a vertex whose vector holds NaN).  The default
         metric is cosine, as in the rest of this class; node2vec_amd.cluster.kmeans defaults to "euclidean".
         Names go through name_id as in most_similar(): a repeated id keeps its last name, an id that name_id does
         not list is a KeyError.  The DataFrame is kept as self.clusters, the KMeansResult as self.kmeans_result."""
-        if self.model is None:
-            raise ValueError("Model is not available. Please run fit()")
-        wv = self.model.wv
-        ids = wv.ids if wv.ids is not None else np.array([int(t) for t in wv.index2word], dtype=np.int64)
-        names = None
-        if self.name_id is not None:
-            names = self.name_id.drop_duplicates("id", keep="last").set_index("id")["name"]
-            missing = ~pd.Index(ids).isin(names.index)
-            if missing.any():
-                raise KeyError(int(ids[missing][0]))
+        wv = self._wv()
+        column, who = self._who(self._vocab_ids(wv))
         self.kmeans_result = wv.kmeans(k, metric=metric, **kw)
-        labels = self.kmeans_result.labels.cpu().numpy()
-        if names is None:
-            self.clusters = pd.DataFrame({"id": ids, "cluster": labels})
-        else:
-            self.clusters = pd.DataFrame({"name": names.reindex(ids).to_numpy(), "cluster": labels})
+        self.clusters = pd.DataFrame({column: who, "cluster": self.kmeans_result.labels.cpu().numpy()})
         self._cluster_metric = metric
         return self.clusters
 
@@ -604,23 +602,13 @@ class _ClusterQueries:
         """self.clusters plus a "silhouette" column: how well every vertex sits in the cluster cluster() gave it
         (model.wv.silhouette of self.kmeans_result, by the metric it was clustered with; NaN for a vertex of no
         cluster).  The mean over the clustered vertices is kept as self.silhouette_score.  cluster() first."""
-        if self.model is None or self.kmeans_result is None:
-            raise ValueError("Model is not available. Please run fit()" if self.model is None else
-                             "Clusters are not available. Please run cluster()")
-        res = self.model.wv.silhouette(self.kmeans_result, metric=self._cluster_metric,
-                                       restrict_vocab=len(self.clusters))
+        wv = self._wv()
+        if self.kmeans_result is None:
+            raise ValueError("Clusters are not available. Please run cluster()")
+        res = wv.silhouette(self.kmeans_result, metric=self._cluster_metric, restrict_vocab=len(self.clusters))
         member = self.kmeans_result.labels >= 0
         self.silhouette_score = float(res.s[member.to(res.s.device)].mean())
         return self.clusters.assign(silhouette=res.s.cpu().numpy())
-
-
-class _LabelQueries:
-    """classify() of a fitted model: what Node2VecHIP and Node2VecSpark share."""
-
-    model = None
-    name_id = None
-    classifier = None
-    label_f1 = None
 
     def classify(self, df_labels: pd.DataFrame, train_fraction: float = 0.5, seed: int = 0, **kw) -> pd.DataFrame:
         """The node2vec paper's multi-label classification (section 4.3): one-vs-rest logistic regression on
@@ -629,18 +617,11 @@ class _LabelQueries:
         class), in vocabulary order: ["id" | "name", "label", "score", "predicted", "train"].  Names go through
         name_id as in cluster().  The LogRegResult is kept as self.classifier, the F1 of the held-out vertices as
         self.label_f1."""
-        if self.model is None:
-            raise ValueError("Model is not available. Please run fit()")
+        wv = self._wv()
         from node2vec_amd import classify
 
-        wv = self.model.wv
-        ids = wv.ids if wv.ids is not None else np.array([int(t) for t in wv.index2word], dtype=np.int64)
-        names = None
-        if self.name_id is not None:
-            names = self.name_id.drop_duplicates("id", keep="last").set_index("id")["name"]
-            missing = ~pd.Index(ids).isin(names.index)
-            if missing.any():
-                raise KeyError(int(ids[missing][0]))
+        ids = self._vocab_ids(wv)
+        column, who = self._who(ids)
         Y, classes = classify.labels_from_frame(df_labels, ids)
         top = kw.pop("top", True)
         X = wv._device_vectors()
@@ -651,63 +632,33 @@ class _LabelQueries:
         train = np.zeros(len(ids), dtype=bool)
         train[classify.split_rows(len(ids), train_fraction, seed)[0]] = True
         c = len(classes)
-        who = ids if names is None else names.reindex(ids).to_numpy()
-        return pd.DataFrame({("id" if names is None else "name"): np.repeat(who, c), "label": np.tile(classes, len(ids)),
+        return pd.DataFrame({column: np.repeat(who, c), "label": np.tile(classes, len(ids)),
                              "score": scores[:, :c].cpu().numpy().reshape(-1),
                              "predicted": pred[:, :c].cpu().numpy().reshape(-1), "train": np.repeat(train, c)})
-
-
-class _ProjectQueries:
-    """project() of a fitted model: what Node2VecHIP and Node2VecSpark share."""
-
-    model = None
-    name_id = None
-    pca_result = None
 
     def project(self, n_components: int = 2, metric: str = "cosine", **kw) -> pd.DataFrame:
         """["id" | "name", "x0", "x1", ..]: every vocabulary vertex on the leading principal components of the
         vectors, in vocabulary order (model.wv.pca and model.wv.project, whose other arguments pass through; NaN:
         a vertex whose vector holds a non-finite value).  The default metric is cosine, as in cluster().  Names go
         through name_id as in cluster().  The PCAResult is kept as self.pca_result."""
-        if self.model is None:
-            raise ValueError("Model is not available. Please run fit()")
-        wv = self.model.wv
-        ids = wv.ids if wv.ids is not None else np.array([int(t) for t in wv.index2word], dtype=np.int64)
-        names = None
-        if self.name_id is not None:
-            names = self.name_id.drop_duplicates("id", keep="last").set_index("id")["name"]
-            missing = ~pd.Index(ids).isin(names.index)
-            if missing.any():
-                raise KeyError(int(ids[missing][0]))
+        wv = self._wv()
+        column, who = self._who(self._vocab_ids(wv))
         self.pca_result = wv.pca(n_components, metric=metric, **kw)
         coords = wv.project(self.pca_result).cpu().numpy()
-        who = {"id": ids} if names is None else {"name": names.reindex(ids).to_numpy()}
-        return pd.DataFrame({**who, **{f"x{j}": coords[:, j] for j in range(coords.shape[1])}})
-
-    tsne_result = None
+        return pd.DataFrame({column: who, **{f"x{j}": coords[:, j] for j in range(coords.shape[1])}})
 
     def tsne(self, **kw) -> pd.DataFrame:
         """["id" | "name", "x0", "x1"]: every vocabulary vertex on the t-SNE map of the vectors, in vocabulary order
         (model.wv.tsne, whose arguments pass through).  Names go through name_id as in project().  The TSNEResult
         is kept as self.tsne_result."""
-        if self.model is None:
-            raise ValueError("Model is not available. Please run fit()")
-        wv = self.model.wv
-        ids = wv.ids if wv.ids is not None else np.array([int(t) for t in wv.index2word], dtype=np.int64)
-        names = None
-        if self.name_id is not None:
-            names = self.name_id.drop_duplicates("id", keep="last").set_index("id")["name"]
-            missing = ~pd.Index(ids).isin(names.index)
-            if missing.any():
-                raise KeyError(int(ids[missing][0]))
+        wv = self._wv()
+        column, who = self._who(self._vocab_ids(wv))  # the whole vocabulary, whatever restrict_vocab leaves
         self.tsne_result = wv.tsne(**kw)
         coords = self.tsne_result.embedding.cpu().numpy()
-        ids = ids[:coords.shape[0]]  # restrict_vocab
-        who = {"id": ids} if names is None else {"name": names.reindex(ids).to_numpy()}
-        return pd.DataFrame({**who, "x0": coords[:, 0], "x1": coords[:, 1]})
+        return pd.DataFrame({column: who[:coords.shape[0]], "x0": coords[:, 0], "x1": coords[:, 1]})
 
 
-class Node2VecHIP(Node2VecBase, _PairQueries, _ClusterQueries, _LabelQueries, _ProjectQueries):
+class Node2VecHIP(Node2VecBase, _ModelQueries):
     """Drop-in for Node2VecGensim (embedding.py:70-178) on one MI355X."""
 
     def __init__(
@@ -829,35 +780,18 @@ class Node2VecHIP(Node2VecBase, _PairQueries, _ClusterQueries, _LabelQueries, _P
         list<float> column, "auto" = lists up to corpus.LIST_COLUMN_MAX_VALUES values per chunk, rows beyond
         (corpus.list_column)"""
         from node2vec_amd import corpus
-        if self.model is None:
-            raise ValueError("Model is not available. Please run fit()")
-        wv = self.model.wv
-        names = None
-        if self.name_id is not None:
-            # embedding.py:139-140 builds a dict: a repeated id keeps its LAST name, and an id
-            # of the vocabulary that name_id does not list is a KeyError
-            names = self.name_id.drop_duplicates("id", keep="last").set_index("id")["name"]
+        wv = self._wv()
+        names = self._names()
         for lo in range(0, len(wv), chunk_rows):
             hi = min(len(wv), lo + chunk_rows)
-            if wv.ids is not None:
-                ids = wv.ids[lo:hi]
-            else:
-                ids = np.array([int(t) for t in wv.index2word[lo:hi]], dtype=np.int64)
             vectors = corpus.list_column(wv.rows(lo, hi), vector_column)
-            if names is not None:
-                missing = ~pd.Index(ids).isin(names.index)
-                if missing.any():
-                    raise KeyError(int(np.asarray(ids)[missing][0]))
-                yield pd.DataFrame({"name": names.reindex(ids).to_numpy(), "vector": vectors})
-            else:
-                yield pd.DataFrame({"id": ids, "vector": vectors})
+            column, who = self._who(self._vocab_ids(wv, lo, hi), names)  # a chunk's KeyError comes with the chunk
+            yield pd.DataFrame({column: who, "vector": vectors})
 
     def embedding(self) -> pd.DataFrame:
         """embedding.py:129-143.  One DataFrame of Python lists, as the reference returns: fine
         up to a few million vertices; beyond 2^31 vector elements use iter_embedding()."""
-        if self.model is None:
-            raise ValueError("Model is not available. Please run fit()")
-        wv = self.model.wv
+        wv = self._wv()
         if len(wv) * max(wv.vector_size, 1) >= 2 ** 31:
             raise MemoryError(f"embedding(): {len(wv)} x {wv.vector_size} values as Python lists do "
                               "not fit a DataFrame; use iter_embedding(chunk_rows) or model.wv.rows()")
@@ -877,18 +811,9 @@ class Node2VecHIP(Node2VecBase, _PairQueries, _ClusterQueries, _LabelQueries, _P
         """The topn vertices nearest to vertex_id by cosine of their vectors (model.wv.most_similar):
         a DataFrame ["id" | "name", "similarity"], names mapped through name_id as in embedding().
         indexer: an index from model.wv.build_index() for an approximate search."""
-        if self.model is None:
-            raise ValueError("Model is not available. Please run fit()")
-        hits = self.model.wv.most_similar(str(vertex_id), topn=topn, indexer=indexer)
-        ids = np.array([int(t) for t, _ in hits], dtype=np.int64)
-        sims = np.array([s for _, s in hits], dtype=np.float64)
-        if self.name_id is None:
-            return pd.DataFrame({"id": ids, "similarity": sims})
-        names = self.name_id.drop_duplicates("id", keep="last").set_index("id")["name"]
-        missing = ~pd.Index(ids).isin(names.index)
-        if missing.any():
-            raise KeyError(int(ids[missing][0]))
-        return pd.DataFrame({"name": names.reindex(ids).to_numpy(), "similarity": sims})
+        hits = self._wv().most_similar(str(vertex_id), topn=topn, indexer=indexer)
+        column, who = self._who(np.array([int(t) for t, _ in hits], dtype=np.int64))
+        return pd.DataFrame({column: who, "similarity": np.array([s for _, s in hits], dtype=np.float64)})
 
     def save_model(self, file_path: str, file_name: str) -> None:
         """embedding.py:153-157: "<path>/<name>.model" """
@@ -931,8 +856,8 @@ class HsW2VModel:
         from node2vec_amd import corpus
 
         wv = self.wv
-        ids = wv.ids if wv.ids is not None else np.array([int(t) for t in wv.index2word], dtype=np.int64)
-        return pd.DataFrame({"word": ids, "vector": corpus.list_column(wv.rows(0, len(wv)), "list")})
+        return pd.DataFrame({"word": _ModelQueries._vocab_ids(wv),
+                             "vector": corpus.list_column(wv.rows(0, len(wv)), "list")})
 
     def save(self, path: str) -> None:
         """a directory (Spark writes one), overwritten"""
@@ -955,7 +880,7 @@ HIP_HS_PARAMS: Dict[str, Any] = {
 }
 
 
-class Node2VecSpark(Node2VecBase, _PairQueries, _ClusterQueries, _LabelQueries, _ProjectQueries):
+class Node2VecSpark(Node2VecBase, _ModelQueries):
     """Drop-in for the reference's Node2VecSpark (embedding.py:182-285) on one MI355X: skip-gram with
     hierarchical softmax, what Spark ML's Word2Vec trains (node2vec_amd/hs.py, csrc/n2v_hs.hip).
 
@@ -1035,8 +960,7 @@ class Node2VecSpark(Node2VecBase, _PairQueries, _ClusterQueries, _LabelQueries, 
     def embedding(self) -> pd.DataFrame:
         """embedding.py:258-267: ["id", "vector"], or ["name", "vector"] through an inner join with
         name_id (ids that name_id does not list are dropped, as Spark's join drops them)"""
-        if self.model is None:
-            raise ValueError("Model is not available. Please run fit()")
+        self._wv()
         df = self.model.getVectors().rename(columns={"word": "id"})
         if self.name_id is not None:
             df = df.merge(self.name_id, on="id", how="inner")[["name", "vector"]]
@@ -1044,9 +968,7 @@ class Node2VecSpark(Node2VecBase, _PairQueries, _ClusterQueries, _LabelQueries, 
 
     def get_vector(self, vertex_id: Union[str, int]) -> pd.DataFrame:
         """embedding.py:269-274: the ["word", "vector"] rows of word == vertex_id (0 or 1 row)"""
-        if self.model is None:
-            raise ValueError("Model is not available. Please run fit()")
-        wv = self.model.wv
+        wv = self._wv()
         row = wv.vocab.get(str(vertex_id))
         if row is None:
             return pd.DataFrame({"word": np.array([], np.int64), "vector": []})

@@ -14,7 +14,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from node2vec_amd import _dense, _lib, similarity
+from node2vec_amd import _dense, _lib
 
 METRICS = {"dot": _lib.PAIR_DOT, "cosine": _lib.PAIR_COSINE}
 OPERATORS = {"average": _lib.PAIR_AVERAGE, "hadamard": _lib.PAIR_HADAMARD, "l1": _lib.PAIR_L1, "l2": _lib.PAIR_L2}
@@ -45,13 +45,7 @@ def pair_scores(X: torch.Tensor, a, b, metric: str = "cosine", inv_norm: Optiona
     n = X.shape[0]
     a, b = _pairs(a, b, n, X.device)
     out = torch.empty(a.shape[0], dtype=torch.float32, device=X.device)
-    norms = None
-    if metric == "cosine":
-        if inv_norm is None:
-            inv_norm = similarity.inv_norms(X)
-        elif inv_norm.ndim != 1 or inv_norm.shape[0] < n:
-            raise ValueError("inv_norm must hold one value per row of X")
-        norms = inv_norm[:n].to(device=X.device, dtype=torch.float32).contiguous()
+    norms = _dense.norms(X, inv_norm) if metric == "cosine" else None
     with torch.cuda.device(X.device):
         _lib.check(_lib.load().n2v_pair_scores(X.data_ptr(), None if norms is None else norms.data_ptr(), n,
                                                X.shape[1], a.data_ptr(), b.data_ptr(), a.shape[0], METRICS[metric],

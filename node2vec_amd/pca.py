@@ -16,7 +16,7 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from node2vec_amd import _dense, _lib, similarity
+from node2vec_amd import _dense, _lib
 
 
 class PCAResult(NamedTuple):
@@ -40,21 +40,6 @@ def slab_rows(n: int, dim: int) -> int:
     return int(_lib.load().n2v_pca_slab_rows(n, dim))
 
 
-def _norms(X: torch.Tensor, unit: bool, inv_norm: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    """the argument check is check_inv_norm's, on the host; this makes the device tensor"""
-    if not unit:
-        return None
-    if inv_norm is None:
-        return similarity.inv_norms(X)
-    return inv_norm[:X.shape[0]].to(device=X.device, dtype=torch.float32).contiguous()
-
-
-def check_inv_norm(n: int, inv_norm) -> None:
-    if inv_norm is not None and (not isinstance(inv_norm, torch.Tensor) or inv_norm.ndim != 1
-                                 or inv_norm.shape[0] < n):
-        raise ValueError("inv_norm must hold one value per row of X")
-
-
 def moments(X: torch.Tensor, center: bool = True, unit: bool = False,
             inv_norm: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, int]:
     """(mean fp64 [dim], S fp64 [dim, dim], n_used): the column means of the used rows (computed whether or not
@@ -62,9 +47,9 @@ def moments(X: torch.Tensor, center: bool = True, unit: bool = False,
     symmetric to the bit.  unit: rows scaled by 1 / norm first (inv_norm: similarity.inv_norms(X), computed when
     not given; passing inv_norm implies nothing without unit=True).  One host synchronisation (n_used)."""
     n, dim = _dense.shape(X)
-    check_inv_norm(n, inv_norm if unit else None)
+    _dense.check_inv_norm(n, inv_norm if unit else None)
     X = _dense.matrix(X)
-    norms = _norms(X, unit, inv_norm)
+    norms = _dense.norms(X, inv_norm) if unit else None
     mean = torch.zeros(dim, dtype=torch.float64, device=X.device)
     S = torch.zeros((dim, dim), dtype=torch.float64, device=X.device)
     used = torch.zeros(2, dtype=torch.int64, device=X.device)
@@ -111,7 +96,7 @@ def fit(X: torch.Tensor, n_components: Optional[int] = None, center: bool = True
     out of range, or a non-finite element of S (an fp32 product or sum of the scatter pass overflowed)."""
     n, dim = _dense.shape(X)
     check_components(n_components, dim)
-    check_inv_norm(n, inv_norm if unit else None)
+    _dense.check_inv_norm(n, inv_norm if unit else None)
     mean, S, n_used = moments(X, center, unit, inv_norm)
     if n_used < 2:
         raise ValueError(f"{n_used} rows of X hold only finite values: principal components need at least 2")
@@ -155,10 +140,10 @@ def transform(X: torch.Tensor, result: PCAResult, inv_norm: Optional[torch.Tenso
     n, dim = _dense.shape(X)
     if not isinstance(result, PCAResult) or result.components.ndim != 2 or result.components.shape[1] != dim:
         raise ValueError(f"result must be a PCAResult whose components are [k, {dim}]")
-    check_inv_norm(n, inv_norm if result.unit else None)
+    _dense.check_inv_norm(n, inv_norm if result.unit else None)
     X = _dense.matrix(X)
     W, b = projection(result)
     if not result.unit:
         return classify.decision_function(X, W, b)
-    norms = _norms(X, True, inv_norm)
+    norms = _dense.norms(X, inv_norm)
     return classify.decision_function(X, W, torch.zeros_like(b)) * norms[:, None] + b

@@ -41,22 +41,11 @@ def _inputs(X, queries, rows, restrict, inv_norm):
         if restrict < 0:
             raise ValueError("restrict must be >= 0")
     n_eff = n if restrict is None else min(restrict, n)
-    if inv_norm is None:
-        inv_norm = inv_norms(X[:n_eff])
-    elif inv_norm.ndim != 1 or inv_norm.shape[0] < n_eff:
-        raise ValueError("inv_norm must hold one value per row of X")
-    inv_norm = inv_norm[:n_eff].to(device=X.device, dtype=torch.float32).contiguous()
+    inv_norm = _dense.norms(X[:n_eff], inv_norm)
     if rows is not None:
-        rows = torch.as_tensor(rows, device=X.device).to(torch.int64).reshape(-1).contiguous()
-        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= n):
-            raise IndexError("query row outside [0, n)")
+        rows = _dense.rows(rows, n, X.device)
     else:
-        queries = torch.as_tensor(queries, device=X.device)
-        if queries.ndim == 1:
-            queries = queries[None]
-        if queries.ndim != 2 or queries.shape[1] != X.shape[1]:
-            raise ValueError(f"queries must be [n_queries, {X.shape[1]}]")
-        queries = queries.to(torch.float32).contiguous()
+        queries = _dense.queries(queries, X.shape[1], X.device)
     if restrict is not None and restrict < n:
         if rows is not None:  # the same q_hat bit for bit: both forms normalise with the same sum
             queries, rows = X[rows].contiguous(), None
@@ -95,22 +84,16 @@ def _topk_fused(X, inv_norm, queries, rows, k):
     L = _lib.load()
     n, dim = X.shape
     nq = (rows if rows is not None else queries).shape[0]
-    out_r = torch.full((nq, k), -1, dtype=torch.int64, device=X.device)
-    out_s = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=X.device)
-    if n == 0 or nq == 0:
-        return out_r, out_s
-    step = nq  # queries per launch: the workspace stays under WORKSPACE_LIMIT
-    while step > 1 and L.n2v_knn_workspace_bytes(n, dim, step, k) > WORKSPACE_LIMIT:
-        step = (step + 1) // 2
-    for i in range(0, nq, step):
-        j = min(nq, i + step)
-        ws = _dense.workspace(L.n2v_knn_workspace_bytes, n, dim, j - i, k, device=X.device)
+
+    def launch(i, j, ws, out_r, out_s):
         q = None if queries is None else queries[i:j]
         r = None if rows is None else rows[i:j]
         _lib.check(L.n2v_knn_topk(X.data_ptr(), inv_norm.data_ptr(), n, dim, _dense.ptr(q), _dense.ptr(r), j - i, k,
                                   out_r[i:j].data_ptr(), out_s[i:j].data_ptr(), ws.data_ptr(), ws.numel(),
                                   _lib.current_stream_ptr()), "n2v_knn_topk")
-    return out_r, out_s
+
+    return _dense.topk_batches(lambda count: L.n2v_knn_workspace_bytes(n, dim, count, k), launch, nq, k, X.device,
+                               empty=n == 0)
 
 
 def _topk_sorted(X, inv_norm, queries, rows, k):
@@ -162,7 +145,4 @@ def knn(X: torch.Tensor, k: int, queries=None, rows=None, restrict: Optional[int
         out_r, out_s = pick(X, inv_norm, queries, qrows, want)
     if not exclude_self:
         return out_r, out_s
-    drop = out_r == self_rows[:, None]
-    drop[:, -1] |= ~drop.any(dim=1)  # not among the k + 1: the last one goes
-    keep = ~drop
-    return out_r[keep].view(-1, k), out_s[keep].view(-1, k)
+    return _dense.drop_self(out_r, out_s, self_rows, k)

@@ -269,7 +269,30 @@ def test_more_probes_never_lower_a_score():
     _same_as_knn((r, s), similarity.knn(Xd, k, rows=R), "nprobe = nlist")
 
 
-# ---- 8. the API ---------------------------------------------------------------------------------------------------
+# ---- 8. query batches ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("nq,by_rows", [(40, False), (37, True)])  # steps of 5: eight launches | seven and a ragged one
+def test_search_splits_a_batch_to_fit_the_workspace(monkeypatch, nq, by_rows):
+    from node2vec_amd import ann, similarity
+
+    rng = np.random.default_rng(70)
+    n, dim, nlist, nprobe, k = 70, 8, 4, 3, 10
+    Xd = _device(ic.mixed_rows(rng, n, dim))
+    idx = ann.build_index(Xd, nlist=nlist, seed=1, max_iter=5)
+    who = {"rows": torch.from_numpy(rng.integers(0, n, nq)).cuda()} if by_rows else \
+        {"queries": _device(rng.standard_normal((nq, dim)))}
+    L = ann._lib.load()
+    real, scans = L.n2v_ivf_topk, []  # the queries of every launch: n2v_ivf_topk's eleventh argument
+    monkeypatch.setattr(L, "n2v_ivf_topk", lambda *args: scans.append(args[10]) or real(*args))
+    whole = ann.search(Xd, idx, k, nprobe=nprobe, **who)
+    need = L.n2v_ivf_workspace_bytes(n, dim, nlist, idx.max_list_rows, 6, nprobe, k)
+    monkeypatch.setattr(similarity, "WORKSPACE_LIMIT", int(need))
+    parts = ann.search(Xd, idx, k, nprobe=nprobe, **who)
+    ic.same(_host(parts), _host(whole), "split")
+    assert scans[0] == nq and len(scans) > 2 and sum(scans[1:]) == nq
+
+
+# ---- 9. the API ---------------------------------------------------------------------------------------------------
 
 def test_keyed_vectors_indexer():
     from node2vec_amd.embedding import KeyedVectors
