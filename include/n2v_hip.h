@@ -1031,16 +1031,17 @@ int n2v_pca_scatter(const float *X, const float *inv_norm, int64_t n, int32_t di
  * "Approximate nearest neighbours").  ADDITIONS ONLY: N2V_ABI_VERSION stays 15.  The index is device data over X in
  * place: list_off int64 [nlist + 1] and row_ids int32 [list_off[nlist]], the rows of X in list order (ascending
  * inside a list); max_list_rows >= the longest list.  probes: int32 [n_queries, nprobe], for every query the lists
- * it scans, -1 for an unused slot; the entries of a query must be distinct.  A query's candidates are the rows of
+ * it scans, -1 for an unused slot; a list a query names twice is refused (below).  A query's candidates are the rows of
  * its probed lists; out_rows / out_scores [n_queries, k] are the k best of them, every score equal to
  * n2v_knn_scores' of the same (query, row) bit for bit, by score descending, then row number ascending; a NaN score
  * is never selected; the tail is row -1, score -inf.  Nothing else is approximate: with every list probed the
  * result is n2v_knn_topk's.  Bounds: X as n2v_knn_*; 1 <= nlist <= 1024; 1 <= nprobe <= nlist; 1 <= k <= 128;
  * 1 <= max_list_rows <= n; n_queries < 2^20; exactly one of queries / query_rows non-NULL.  Argument errors are
  * N2V_EINVAL before any launch; n == 0 or n_queries == 0 is N2V_OK and launches nothing.  A list longer than
- * max_list_rows, offsets that descend, a probe outside [-1, nlist) or a row id outside [0, n) sets N2V_ST_RANGE in
- * status[0] (a device word, read after synchronising): the call still runs, reads nothing out of bounds, and its
- * results must be discarded. */
+ * max_list_rows, offsets that descend, a probe outside [-1, nlist), a list number that an earlier entry of the same
+ * query's probes names already, or a row id outside [0, n) sets N2V_ST_RANGE in status[0] (a device word, read after
+ * synchronising): such a probe is skipped like an unused slot, the call still runs, reads nothing out of bounds or
+ * uninitialised, and its results must be discarded. */
 
 /* Bytes of workspace n2v_ivf_topk needs; -1 for sizes it refuses (also: more scan blocks than one launch takes --
  * split the queries), 0 for n == 0 or n_queries == 0.  Non-decreasing in n_queries, nprobe and k. */
@@ -1073,8 +1074,9 @@ int n2v_ivf_topk(const float *X, const float *inv_norm, int64_t n, int32_t dim, 
  * descending, then row number ascending; a NaN score (a NaN coarse score, a NaN table entry) is never selected;
  * the tail is row -1, score -inf.  Bounds and status as n2v_ivf_topk: 1 <= k <= 128, argument errors N2V_EINVAL
  * before any launch, n == 0 or n_queries == 0 N2V_OK without a launch; a list longer than max_list_rows, offsets
- * that descend, a probe outside [-1, nlist) or a row id outside [0, n) sets N2V_ST_RANGE in status[0]: the call
- * still runs, reads nothing out of bounds, and its results must be discarded. */
+ * that descend, a probe outside [-1, nlist), a list number a query's probes repeat, or a row id outside [0, n) sets
+ * N2V_ST_RANGE in status[0]: the call still runs, reads nothing out of bounds or uninitialised, and its results must
+ * be discarded. */
 
 /* Bytes of workspace n2v_ivfpq_topk needs (q_hat, fp32 [n_queries, m, 256] tables, the grouping tables, the slots);
  * -1 for sizes it refuses (also: more scan blocks than one launch takes -- split the queries), 0 for n == 0 or

@@ -150,8 +150,9 @@ def _scan(name, need, launch, nq, k, device, empty):
 
     out = _dense.topk_batches(need, run, nq, k, device, max_step=(1 << 20) - 1, empty=empty)
     if status and int(status[0]) & _lib.ST_RANGE:
-        raise ValueError(f"{name}: a list longer than max_list_rows, a probe outside [-1, nlist) or a row id "
-                         "outside [0, n): the index does not belong to these arguments")
+        raise ValueError(f"{name}: a list longer than max_list_rows, a probe outside [-1, nlist), a list that a "
+                         "query's probes name twice, or a row id outside [0, n): the index does not belong to "
+                         "these arguments")
     return out
 
 
@@ -222,7 +223,8 @@ def search(X: torch.Tensor, index: IVFIndex, k: int, queries=None, rows=None, np
     """similarity.knn's contract over the rows of the probed lists: (rows int64 [nq, k], scores fp32 [nq, k]), by
     score descending, then row ascending; where fewer than k candidates exist the tail is row -1, score -inf; a NaN
     score is never selected.  X: the matrix the index was built on.  nprobe: lists per query (default: the index's);
-    probes: int32 [nq, nprobe'] of list numbers (-1: unused, a query's entries distinct) instead of probe()'s.
+    probes: int32 [nq, nprobe'] of list numbers (-1: unused; a list a query names twice: ValueError, found on the
+    device and raised after the scan like a probe out of range) instead of probe()'s.
     exclude_self (rows= only): a query's own row is not returned (k + 1 are asked for).  k + exclude_self <= 128."""
     k, want, X, inv_norm, queries, qrows, probes = _front(IVFIndex, index, k, 0, queries, rows, X, inv_norm, probes,
                                                           exclude_self)
@@ -450,7 +452,8 @@ def search_pq(index: IVFPQIndex, k: int, queries=None, rows=None, X: Optional[to
     refine = 0: the approximate result.  The score of a listed row is the query's score against its list's
     centroid plus m table entries (n2v_ivfpq_topk), ordered by score descending, then row ascending.  X is needed
     only with rows=, to fetch the query vectors.  The centroid scores are the probe's own (similarity.knn over the
-    centroids), or with probes= (int32 [nq, nprobe'], -1: unused) similarity.scores over the centroids, gathered.
+    centroids), or with probes= (int32 [nq, nprobe'], -1: unused; a list a query names twice: ValueError, as in
+    search) similarity.scores over the centroids, gathered.
     refine = f >= 1 (X required): the min(128, f * k') best by approximate score (k' = k + exclude_self) are scored
     again with similarity.knn's scores, bit for bit, and the k best by (exact score descending, row ascending)
     returned -- a NaN score is dropped there.  exclude_self (rows= only): a query's own row is not returned.

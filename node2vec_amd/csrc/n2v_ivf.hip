@@ -192,8 +192,8 @@ int n2v_ivf_topk(const float *X, const float *inv_norm, int64_t n, int32_t dim, 
   hipStream_t st = (hipStream_t)stream;
   const int rc = launch_queries(X, inv_norm, dim, queries, query_rows, n_queries, p.qhat, st);
   if (rc != N2V_OK) return rc;
-  const int rg = launch_groups(p.g, list_off, nlist, max_list_rows, probes, p.pairs, p.qt, p.pairs * p.chunks * k, p.s0,
-                              p.r0, status, st);
+  const int rg = launch_groups(p.g, list_off, nlist, max_list_rows, probes, p.pairs, nprobe, p.qt,
+                              p.pairs * p.chunks * k, p.s0, p.r0, status, st);
   if (rg != N2V_OK) return rg;
   if (p.qt == 64)
     launch_scan<4, 64>(p, X, inv_norm, n, dim, list_off, row_ids, nlist, max_list_rows, n_queries, nprobe, k, status, st);

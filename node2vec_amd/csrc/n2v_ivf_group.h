@@ -54,14 +54,27 @@ __device__ inline bool probe_ok(int32_t l, int32_t nlist, uint32_t *status) {
   return false;
 }
 
+// Entry i of probes [n_queries][nprobe] as the scans take it: a list number that no earlier entry of the same query
+// names.  A repeated list sets N2V_ST_RANGE and is skipped like a probe out of range, so that a query's slots never
+// hold a row twice (merge_kernel relies on it).  Both grouping kernels decide by this one function.
+__device__ inline bool probe_taken(const int32_t *__restrict__ probes, int64_t i, int32_t nprobe, int32_t nlist,
+                                   uint32_t *status) {
+  const int32_t l = probes[i];
+  if (!probe_ok(l, nlist, status)) return false;
+  for (int64_t j = i - i % nprobe; j < i; ++j)
+    if (probes[j] == l) {
+      atomicOr(status, N2V_ST_RANGE);
+      return false;
+    }
+  return true;
+}
+
 __global__ __launch_bounds__(256) void ivf_count_kernel(const int32_t *__restrict__ probes, int64_t pairs,
-                                                        int32_t nlist, int32_t *__restrict__ cnt,
+                                                        int32_t nprobe, int32_t nlist, int32_t *__restrict__ cnt,
                                                         uint32_t *__restrict__ status) {
   const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < pairs; i += stride) {
-    const int32_t l = probes[i];
-    if (probe_ok(l, nlist, status)) atomicAdd(&cnt[l], 1);
-  }
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < pairs; i += stride)
+    if (probe_taken(probes, i, nprobe, nlist, status)) atomicAdd(&cnt[probes[i]], 1);
 }
 
 // pair_off / tile_off: the exclusive sums over the lists of the pairs and of the tiles of qt pairs; one block
@@ -92,14 +105,16 @@ __global__ __launch_bounds__(kMaxLists) void ivf_scan_kernel(const int32_t *__re
 }
 
 __global__ __launch_bounds__(256) void ivf_group_kernel(const int32_t *__restrict__ probes, int64_t pairs,
-                                                        int32_t nlist, const int32_t *__restrict__ pair_off,
-                                                        int32_t *__restrict__ cursor,
-                                                        int32_t *__restrict__ pair_list) {
+                                                        int32_t nprobe, int32_t nlist,
+                                                        const int32_t *__restrict__ pair_off,
+                                                        int32_t *__restrict__ cursor, int32_t *__restrict__ pair_list,
+                                                        uint32_t *__restrict__ status) {
   const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < pairs; i += stride) {
-    const int32_t l = probes[i];
-    if (l >= 0 && l < nlist) pair_list[pair_off[l] + atomicAdd(&cursor[l], 1)] = (int32_t)i;
-  }
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < pairs; i += stride)
+    if (probe_taken(probes, i, nprobe, nlist, status)) {
+      const int32_t l = probes[i];
+      pair_list[pair_off[l] + atomicAdd(&cursor[l], 1)] = (int32_t)i;
+    }
 }
 
 inline unsigned blocks_for(int64_t items) {
@@ -109,17 +124,18 @@ inline unsigned blocks_for(int64_t items) {
 
 // the launches that come before a scan: the slots emptied and the bounds checked, then count, scan, fill
 inline int launch_groups(const IvfGroups &g, const int64_t *list_off, int32_t nlist, int64_t max_list_rows,
-                         const int32_t *probes, int64_t pairs, int32_t qt, int64_t entries, float *part_s,
-                         int32_t *part_r, uint32_t *status, hipStream_t st) {
+                         const int32_t *probes, int64_t pairs, int32_t nprobe, int32_t qt, int64_t entries,
+                         float *part_s, int32_t *part_r, uint32_t *status, hipStream_t st) {
   hipLaunchKernelGGL(ivf_prepare_kernel, dim3(blocks_for(entries)), dim3(256), 0, st, list_off, nlist, max_list_rows,
                      entries, part_s, part_r, g.cnt, g.cursor, status);
   N2V_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(ivf_count_kernel, dim3(blocks_for(pairs)), dim3(256), 0, st, probes, pairs, nlist, g.cnt, status);
+  hipLaunchKernelGGL(ivf_count_kernel, dim3(blocks_for(pairs)), dim3(256), 0, st, probes, pairs, nprobe,
+                     nlist, g.cnt, status);
   N2V_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), dim3(kMaxLists), 0, st, g.cnt, nlist, qt, g.pair_off, g.tile_off);
   N2V_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(ivf_group_kernel, dim3(blocks_for(pairs)), dim3(256), 0, st, probes, pairs, nlist, g.pair_off,
-                     g.cursor, g.pair_list);
+  hipLaunchKernelGGL(ivf_group_kernel, dim3(blocks_for(pairs)), dim3(256), 0, st, probes, pairs, nprobe, nlist,
+                     g.pair_off, g.cursor, g.pair_list, status);
   N2V_HIP_CHECK(hipGetLastError());
   return N2V_OK;
 }

@@ -319,8 +319,8 @@ int n2v_ivfpq_topk(const uint8_t *codes, const float *codebooks, int32_t m, cons
   if (rc != N2V_OK) return rc;
   rc = launch_lut(p.qhat, n_queries, dim, codebooks, m, p.lut, st);
   if (rc != N2V_OK) return rc;
-  rc = launch_groups(p.g, list_off, nlist, max_list_rows, probes, p.pairs, p.qt, p.pairs * p.chunks * k, p.s0, p.r0,
-                     status, st);
+  rc = launch_groups(p.g, list_off, nlist, max_list_rows, probes, p.pairs, nprobe, p.qt, p.pairs * p.chunks * k, p.s0,
+                     p.r0, status, st);
   if (rc != N2V_OK) return rc;
 #define N2V_PQ_SCAN(T, W) \
   launch_pq_scan<T, W>(p, codes, m, n, list_off, row_ids, nlist, max_list_rows, coarse, nprobe, k, status, st)
