@@ -1002,6 +1002,39 @@ int n2v_logreg_loss_grad(const float *X, const uint32_t *y_bits, int64_t n, int3
                          const float *b, int32_t c, double *loss_out, double *grad_w_out, double *grad_b_out,
                          void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The link-prediction classifier (node2vec paper, section 4.4; csrc/n2v_edge_logreg.hip, DESIGN.md
+ * "Link-prediction classifier"): binary logistic regression on the edge feature f = op(x_a, x_b) of a list of pairs,
+ * without the [n_pairs, dim] feature matrix.  ADDITIONS ONLY: N2V_ABI_VERSION stays 15.
+ * X: row-major fp32 [n, dim], 1 <= dim <= 1024, 0 <= n < 2^31; a, b: int64 [n_pairs] row numbers, 0 <= n_pairs <
+ * 2^31; y: uint8 [n_pairs], nonzero is a positive; w: fp32 [dim]; b0: one fp32, by pointer (device memory); op: one
+ * of N2V_PAIR_AVERAGE .. N2V_PAIR_L2.  f[d] are the bits n2v_pair_features writes; z = dot(w, f) + b0, dot in the
+ * fixed order of n2v_pair_scores with (w, f) in the place of (x_a, x_b); the logistic functions are those of
+ * n2v_logreg_*.  Every result is a function of the arguments alone, bit for bit, and does not change when a and b
+ * are swapped (no float atomics; the order of summation is written out in csrc/n2v_edge_logreg.hip and restated in
+ * tests/cpu_edge_logreg/n2v_edge_logreg_cpu.c).  Both calls only read X.  A pair with an index outside [0, n) is
+ * never dereferenced: its score is NaN, and so are a loss and a gradient that include it.
+ * Argument errors are N2V_EINVAL before any launch: sizes out of range, an unknown op, then (n_pairs > 0) a NULL
+ * pointer, then a workspace that is NULL, not 16-byte aligned or smaller than n2v_edge_logreg_workspace_bytes.
+ * n_pairs == 0 is N2V_OK, launches nothing and writes nothing. */
+
+/* Pairs per slab of the gradient's fixed order of summation: n2v_logreg_slab_rows(n_pairs, dim, 1) (a multiple of
+ * 64; -1 for sizes the calls refuse). */
+int64_t n2v_edge_logreg_slab_pairs(int64_t n_pairs, int32_t dim);
+/* Bytes of workspace of n2v_edge_logreg_loss_grad (-1 for sizes it refuses, 0 for n_pairs == 0): per slab (at most
+ * 2048 of them) fp32 [dim] and [1] and fp64 [1] partials, each part rounded up to 256 bytes. */
+int64_t n2v_edge_logreg_workspace_bytes(int64_t n_pairs, int32_t dim);
+/* z_out[i] = z of pair i, fp32 [n_pairs]. */
+int n2v_edge_logreg_scores(const float *X, int64_t n, int32_t dim, const int64_t *a, const int64_t *b,
+                           int64_t n_pairs, int32_t op, const float *w, const float *b0, float *z_out,
+                           void *stream);
+/* One pass over the pairs: loss_out[0] = sum over i of the logistic loss l(z_i, y_i), grad_w_out[d] = sum_i
+ * (sigmoid(z_i) - y_i) f_i[d] (fp64 [dim]), grad_b_out[0] = sum_i (sigmoid(z_i) - y_i): unregularised sums, not
+ * means; fp32 chains per slab of pairs, folded over the slabs in fp64. */
+int n2v_edge_logreg_loss_grad(const float *X, int64_t n, int32_t dim, const int64_t *a, const int64_t *b,
+                              const uint8_t *y, int64_t n_pairs, int32_t op, const float *w, const float *b0,
+                              double *loss_out, double *grad_w_out, double *grad_b_out, void *workspace,
+                              int64_t workspace_bytes, void *stream);
+
 /* The moments principal components need (csrc/n2v_pca.hip, DESIGN.md "Principal components").  ADDITIONS ONLY:
  * N2V_ABI_VERSION stays 15.  X: row-major fp32 [n, dim], 1 <= dim <= 1024, 0 <= n < 2^31; inv_norm: fp32 [n] or
  * NULL.  Row r enters as xh[d] = x[d] * inv_norm[r] (one fp32 multiply; NULL: x[d]) and is USED when all dim values

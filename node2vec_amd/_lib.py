@@ -36,7 +36,9 @@ SYMBOLS = ("n2v_abi_version", "n2v_status_string", "n2v_device_count", "n2v_alia
            "n2v_rank_pairs_build", "n2v_cbow_train", "n2v_cbow_hogwild_waves", "n2v_pair_scores",
            "n2v_pair_features", "n2v_pairs_in_graph", "n2v_kmeans_slab_rows", "n2v_kmeans_workspace_bytes",
            "n2v_kmeans_assign", "n2v_kmeans_update", "n2v_kmeans_step", "n2v_logreg_slab_rows",
-           "n2v_logreg_workspace_bytes", "n2v_logreg_scores", "n2v_logreg_loss_grad", "n2v_pca_slab_rows",
+           "n2v_logreg_workspace_bytes", "n2v_logreg_scores", "n2v_logreg_loss_grad", "n2v_edge_logreg_slab_pairs",
+           "n2v_edge_logreg_workspace_bytes", "n2v_edge_logreg_scores", "n2v_edge_logreg_loss_grad",
+           "n2v_pca_slab_rows",
            "n2v_pca_workspace_bytes", "n2v_pca_mean", "n2v_pca_scatter", "n2v_ivf_workspace_bytes", "n2v_ivf_plan",
            "n2v_ivf_topk", "n2v_silhouette_workspace_bytes", "n2v_silhouette", "n2v_tsne_plan",
            "n2v_tsne_workspace_bytes", "n2v_tsne_repulse", "n2v_tsne_step", "n2v_ivfpq_workspace_bytes",
@@ -280,6 +282,17 @@ def load():
     L.n2v_logreg_loss_grad.restype = C.c_int
     L.n2v_logreg_loss_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.n2v_edge_logreg_slab_pairs.restype = C.c_int64
+    L.n2v_edge_logreg_slab_pairs.argtypes = [C.c_int64, C.c_int32]
+    L.n2v_edge_logreg_workspace_bytes.restype = C.c_int64
+    L.n2v_edge_logreg_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+    L.n2v_edge_logreg_scores.restype = C.c_int
+    L.n2v_edge_logreg_scores.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.n2v_edge_logreg_loss_grad.restype = C.c_int
+    L.n2v_edge_logreg_loss_grad.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.n2v_pca_slab_rows.restype = C.c_int64
     L.n2v_pca_slab_rows.argtypes = [C.c_int64, C.c_int32]
     L.n2v_pca_workspace_bytes.restype = C.c_int64

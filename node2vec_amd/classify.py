@@ -151,6 +151,61 @@ def two_loop(g: torch.Tensor, pairs) -> torch.Tensor:
     return -q
 
 
+def lbfgs(evaluate_at: Callable, shape: Tuple[int, int], n: int, max_iter: int, tol: float, history: int):
+    """The host-driven L-BFGS of fit() and linkpred.fit_edges(): minimises from theta = 0 (fp32, `shape` = [c, dim + 1])
+    the objective evaluate_at(theta) -> (f, g float64 of `shape`, max |g|).  `history` pairs, Armijo backtracking
+    (c1 = 1e-4, halving, at most 30 halvings, first step 1 / max(1, |g|)), in float64; the iterate is fp32:
+    theta+ = float32(theta + alpha d), s from the rounded values; a pair enters the history only if s.y > 0.  Stops
+    when max |g| / n <= tol ("gradient"), after max_iter iterations ("max_iter") or when the line search fails
+    ("line_search").  -> (theta, f, max |g|, n_iter, n_evals, reason)"""
+    theta = torch.zeros(shape, dtype=torch.float32)
+    f, g, gmax = evaluate_at(theta)
+    n_evals = 1
+    pairs = []
+    n_iter, reason = 0, "max_iter"
+    while True:
+        if gmax / n <= tol:
+            reason = "gradient"
+            break
+        if n_iter >= int(max_iter):
+            break
+        d = two_loop(g, pairs)
+        slope = float((g * d).sum())
+        if not slope < 0.0:  # not a descent direction: restart from steepest descent
+            pairs, d = [], -g
+            slope = float((g * d).sum())
+        alpha = 1.0 if pairs else 1.0 / max(1.0, float(g.norm()))
+        for _ in range(MAX_HALVINGS + 1):
+            nxt = (theta.double() + alpha * d).to(torch.float32)
+            f_new, g_new, gmax_new = evaluate_at(nxt)
+            n_evals += 1
+            if f_new <= f + ARMIJO_C1 * alpha * slope:  # false for NaN
+                break
+            alpha *= 0.5
+        else:
+            reason = "line_search"
+            break
+        s = nxt.double() - theta.double()
+        y = g_new - g
+        if float((s * y).sum()) > 0.0:
+            pairs = (pairs + [(s, y)])[-int(history):]
+        theta, f, g, gmax = nxt, f_new, g_new, gmax_new
+        n_iter += 1
+    return theta, f, gmax, n_iter, n_evals, reason
+
+
+def regularised(loss_grad_fn: Callable, c: int, dim: int, lam: float) -> Callable:
+    """lbfgs's evaluate_at for f = loss + lam |W|^2 / 2 over theta = [W | b] (the bias is not penalised), from
+    loss_grad_fn(W, b) -> (loss, gW, gb), the unregularised sums"""
+    def evaluate_at(th):
+        loss, gW, gb = loss_grad_fn(th[:, :dim].contiguous(), th[:, dim].contiguous())
+        w64 = th[:, :dim].double()
+        g = torch.cat([gW.cpu().double().view(c, dim) + lam * w64, gb.cpu().double().view(c, 1)], 1)
+        f = float(loss.cpu().double().reshape(())) + 0.5 * lam * float((w64 * w64).sum())
+        return f, g, float(g.abs().max())
+    return evaluate_at
+
+
 def fit(X: torch.Tensor, Y: torch.Tensor, C: float = 1.0, max_iter: int = 100, tol: float = 1e-4, history: int = 10,
         loss_grad_fn: Optional[Callable] = None) -> LogRegResult:
     """One-vs-rest L2 logistic regression from W = 0, b = 0: minimises f = sum of the logistic losses +
@@ -180,49 +235,8 @@ def fit(X: torch.Tensor, Y: torch.Tensor, C: float = 1.0, max_iter: int = 100, t
             return flat[:1], flat[1:1 + c * dim], flat[1 + c * dim:]
     if not bool(torch.isfinite(X).all()):
         raise ValueError("X holds a non-finite value")
-    lam = 1.0 / float(C)
-    theta = torch.zeros((c, dim + 1), dtype=torch.float32)
-    n_evals = 0
-
-    def evaluate_at(th):
-        nonlocal n_evals
-        n_evals += 1
-        loss, gW, gb = loss_grad_fn(th[:, :dim].contiguous(), th[:, dim].contiguous())
-        w64 = th[:, :dim].double()
-        g = torch.cat([gW.cpu().double().view(c, dim) + lam * w64, gb.cpu().double().view(c, 1)], 1)
-        f = float(loss.cpu().double().reshape(())) + 0.5 * lam * float((w64 * w64).sum())
-        return f, g, float(g.abs().max())
-
-    f, g, gmax = evaluate_at(theta)
-    pairs = []
-    n_iter, reason = 0, "max_iter"
-    while True:
-        if gmax / n <= tol:
-            reason = "gradient"
-            break
-        if n_iter >= int(max_iter):
-            break
-        d = two_loop(g, pairs)
-        slope = float((g * d).sum())
-        if not slope < 0.0:  # not a descent direction: restart from steepest descent
-            pairs, d = [], -g
-            slope = float((g * d).sum())
-        alpha = 1.0 if pairs else 1.0 / max(1.0, float(g.norm()))
-        for _ in range(MAX_HALVINGS + 1):
-            nxt = (theta.double() + alpha * d).to(torch.float32)
-            f_new, g_new, gmax_new = evaluate_at(nxt)
-            if f_new <= f + ARMIJO_C1 * alpha * slope:  # false for NaN
-                break
-            alpha *= 0.5
-        else:
-            reason = "line_search"
-            break
-        s = nxt.double() - theta.double()
-        y = g_new - g
-        if float((s * y).sum()) > 0.0:
-            pairs = (pairs + [(s, y)])[-int(history):]
-        theta, f, g, gmax = nxt, f_new, g_new, gmax_new
-        n_iter += 1
+    theta, f, gmax, n_iter, n_evals, reason = lbfgs(regularised(loss_grad_fn, c, dim, 1.0 / float(C)), (c, dim + 1),
+                                                    n, max_iter, tol, history)
     dev = X.device
     return LogRegResult(theta[:, :dim].contiguous().to(dev), theta[:, dim].contiguous().to(dev), f, gmax, n_iter,
                         n_evals, reason == "gradient", reason)

@@ -382,6 +382,25 @@ class KeyedVectors:
         return linkpred.pair_features(self._device_vectors(), torch.from_numpy(ra), torch.from_numpy(rb),
                                       op).cpu().numpy()
 
+    def fit_edges(self, tokens_a, tokens_b, y, op: str = "hadamard", **kw):
+        """the node2vec paper's link-prediction classifier on the pairs (tokens_a[i], tokens_b[i]) with labels y
+        (nonzero: an edge): linkpred.fit_edges on the vectors, whose other arguments pass through -> EdgeClassifier"""
+        from node2vec_amd import linkpred
+
+        if op not in linkpred.OPERATORS:
+            raise ValueError(f"operator {op!r}: " + " | ".join(linkpred.OPERATORS))
+        ra, rb = self._pair_rows(tokens_a, tokens_b)
+        return linkpred.fit_edges(self._device_vectors(), torch.from_numpy(ra), torch.from_numpy(rb),
+                                  torch.as_tensor(np.asarray(y)), op=op, **kw)
+
+    def edge_scores(self, tokens_a, tokens_b, result) -> np.ndarray:
+        """the score of every pair under a fitted EdgeClassifier, fp32 [n]: dot(w, op(x_a, x_b)) + b (> 0: an edge)"""
+        from node2vec_amd import linkpred
+
+        ra, rb = self._pair_rows(tokens_a, tokens_b)
+        return linkpred.edge_scores(self._device_vectors(), torch.from_numpy(ra), torch.from_numpy(rb), result.w,
+                                    result.b, result.op).cpu().numpy()
+
     def kmeans(self, k: int, metric: str = "cosine", restrict_vocab: Optional[int] = None, **kw):
         """k-means of the vectors on the GPU (node2vec_amd.cluster.kmeans, whose other arguments pass through):
         a KMeansResult whose labels[i] is the cluster of row i (token index2word[i]).  The default metric is
@@ -523,9 +542,9 @@ def _check_objective(p: Dict[str, Any]) -> None:
 
 class _ModelQueries:
     """The queries of a fitted model that Node2VecHIP and Node2VecSpark share: link_scores() / edge_embedding(),
-    cluster() / silhouette(), classify(), project() and tsne().  They answer per vertex in vocabulary order, under
-    ["id"], or ["name"] through name_id: a repeated id keeps its last name, and an id of the vocabulary that
-    name_id does not list is a KeyError -- raised before any GPU work."""
+    link_classifier() / link_classifier_scores(), cluster() / silhouette(), classify(), project() and tsne().  They
+    answer per vertex in vocabulary order, under ["id"], or ["name"] through name_id: a repeated id keeps its last
+    name, and an id of the vocabulary that name_id does not list is a KeyError -- raised before any GPU work."""
 
     model = None
     name_id = None
@@ -534,6 +553,7 @@ class _ModelQueries:
     silhouette_score = None
     _cluster_metric = "cosine"
     classifier = None
+    edge_classifier = None
     label_f1 = None
     pca_result = None
     tsne_result = None
@@ -584,6 +604,26 @@ class _ModelQueries:
         src, dst = self._edge_ids(df_edges)
         vectors = corpus.list_column(self.model.wv.edge_features(src, dst, operator))
         return pd.DataFrame({"src": src, "dst": dst, "vector": vectors})
+
+    def link_classifier(self, df_pairs: pd.DataFrame, operator: str = "hadamard", **kw):
+        """The node2vec paper's link-prediction classifier (section 4.4): logistic regression on the edge feature of
+        every row's pair of vertices, df_pairs holding ["src", "dst", "label"] (label nonzero: an edge)
+        (model.wv.fit_edges, whose other arguments pass through).  Returns the EdgeClassifier, kept as
+        self.edge_classifier."""
+        src, dst = self._edge_ids(df_pairs)
+        if "label" not in df_pairs.columns:
+            raise ValueError('df_pairs must have the column "label"')
+        self.edge_classifier = self.model.wv.fit_edges(src, dst, df_pairs["label"].to_numpy(), op=operator, **kw)
+        return self.edge_classifier
+
+    def link_classifier_scores(self, df_edges: pd.DataFrame, result=None) -> pd.DataFrame:
+        """["src", "dst", "score"]: the score of every row's pair of vertices under `result` (an EdgeClassifier;
+        default: the one link_classifier() kept) (model.wv.edge_scores)"""
+        src, dst = self._edge_ids(df_edges)
+        result = self.edge_classifier if result is None else result
+        if result is None:
+            raise ValueError("No classifier is available. Please run link_classifier()")
+        return pd.DataFrame({"src": src, "dst": dst, "score": self.model.wv.edge_scores(src, dst, result)})
 
     def cluster(self, k: int, metric: str = "cosine", **kw) -> pd.DataFrame:
         """["id" | "name", "cluster"]: the k-means cluster of every vocabulary vertex, in vocabulary order

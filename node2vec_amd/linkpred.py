@@ -1,4 +1,5 @@
-"""Link prediction over trained vectors, on the GPU (csrc/n2v_pairs.hip): the node2vec paper's headline task.
+"""Link prediction over trained vectors, on the GPU (csrc/n2v_pairs.hip, csrc/n2v_edge_logreg.hip): the node2vec
+paper's headline task.
 
 Scores of a list of vertex pairs (dot or cosine), the paper's four edge features (Table 1: average, hadamard,
 l1, l2), membership of pairs in a DeviceGraph, seeded samples of edges and of non-edges, and the exact AUC
@@ -6,10 +7,16 @@ l1, l2), membership of pairs in a DeviceGraph, seeded samples of edges and of no
 symmetric in the pair, so it does not depend on how pairs are batched (DESIGN.md "Link prediction").  Only the
 output is ever allocated: no [pairs, dim] gather of either side is made.
 
+The paper's own protocol (section 4.4) trains a binary classifier on the edge feature op(x_a, x_b): fit_edges() does
+that with the L-BFGS of node2vec_amd.classify over a fused kernel that gathers the two rows of a pair, forms the
+feature in registers and accumulates the loss and gradient in one fixed order -- no feature row ever reaches memory
+(DESIGN.md "Link-prediction classifier").  edge_scores() scores pairs with the fitted weights, link_classifier_auc()
+runs the whole protocol.
+
 Device tensors in and out.  There is no CPU path for the kernels: a missing GPU or library raises.  auc() is
 plain torch and works on CPU tensors too.
 """
-from typing import Dict, Optional, Tuple
+from typing import Callable, Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -186,3 +193,167 @@ def link_auc(graph, wv, n_pairs: int, seed: int, metric: str = "cosine", center:
         scores.append(pair_scores(X, ra[keep], rb[keep], metric, inv_norm=inv_norm))
     return {"auc": auc(scores[0], scores[1]), "pairs_pos": int(scores[0].numel()),
             "pairs_neg": int(scores[1].numel()), "dropped": dropped}
+
+
+class EdgeClassifier(NamedTuple):
+    w: torch.Tensor      # fp32 [dim]
+    b: torch.Tensor      # fp32 [1]
+    op: str              # the edge feature the weights belong to
+    loss: float          # the objective at (w, b): sum of the logistic losses + |w|^2 / (2 C)
+    grad_max: float      # max |gradient of the objective| at (w, b)
+    n_iter: int
+    n_evals: int         # passes over the pairs
+    converged: bool
+    reason: str          # "gradient" | "max_iter" | "line_search"
+
+
+def _operator(op: str) -> int:
+    if op not in OPERATORS:
+        raise ValueError(f"operator {op!r}: " + " | ".join(OPERATORS))
+    return OPERATORS[op]
+
+
+def _weights(w, b0, dim: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    w = torch.as_tensor(w)
+    if w.ndim != 1 or w.shape[0] != dim:
+        raise ValueError(f"w must be a [{dim}] tensor")
+    b0 = torch.as_tensor(b0)
+    if b0.numel() != 1:
+        raise ValueError("b0 must be one value")
+    return (w.to(device=device, dtype=torch.float32).contiguous(),
+            b0.to(device=device, dtype=torch.float32).reshape(1).contiguous())
+
+
+def _labels(y, n_pairs: int, device) -> torch.Tensor:
+    """uint8 [n_pairs] on `device`: 1 where y is nonzero"""
+    y = torch.as_tensor(y, device=device).reshape(-1)
+    if y.shape[0] != n_pairs:
+        raise ValueError(f"y must hold one label per pair ({n_pairs}), not {y.shape[0]}")
+    return (y != 0).to(torch.uint8).contiguous()
+
+
+def edge_slab_pairs(n_pairs: int, dim: int) -> int:
+    """pairs per slab of the gradient's fixed order of summation (n2v_edge_logreg_slab_pairs)"""
+    return int(_lib.load().n2v_edge_logreg_slab_pairs(n_pairs, dim))
+
+
+def alloc_edge_workspace(n_pairs: int, dim: int, device) -> torch.Tensor:
+    return _dense.workspace(_lib.load().n2v_edge_logreg_workspace_bytes, n_pairs, dim, device=device)
+
+
+def edge_scores(X: torch.Tensor, a, b, w, b0, op: str = "hadamard") -> torch.Tensor:
+    """z of every pair, fp32 [n_pairs]: dot(w, op(x_a, x_b)) + b0, the feature formed in registers
+    (n2v_edge_logreg_scores).  The dot is pair_scores' fixed order with (w, feature) in the place of the two rows."""
+    code = _operator(op)
+    X = _dense.matrix(X)
+    n, dim = X.shape
+    a, b = _pairs(a, b, n, X.device)
+    w, b0 = _weights(w, b0, dim, X.device)
+    out = torch.empty(a.shape[0], dtype=torch.float32, device=X.device)
+    with torch.cuda.device(X.device):
+        _lib.check(_lib.load().n2v_edge_logreg_scores(X.data_ptr(), n, dim, a.data_ptr(), b.data_ptr(), a.shape[0],
+                                                      code, w.data_ptr(), b0.data_ptr(), out.data_ptr(),
+                                                      _lib.current_stream_ptr()), "n2v_edge_logreg_scores")
+    return out
+
+
+def _edge_loss_grad_flat(X, a, b, y, w, b0, code: int, workspace=None) -> torch.Tensor:
+    """float64 [1 + dim + 1] on the device: loss, gw, gb.  X, a, b, y as the checked device tensors."""
+    n, dim = X.shape
+    w, b0 = _weights(w, b0, dim, X.device)
+    out = torch.zeros(dim + 2, dtype=torch.float64, device=X.device)
+    with torch.cuda.device(X.device):
+        ws = workspace if workspace is not None else alloc_edge_workspace(a.shape[0], dim, X.device)
+        _lib.check(_lib.load().n2v_edge_logreg_loss_grad(X.data_ptr(), n, dim, a.data_ptr(), b.data_ptr(),
+                                                         y.data_ptr(), a.shape[0], code, w.data_ptr(), b0.data_ptr(),
+                                                         out.data_ptr(), out[1:].data_ptr(), out[1 + dim:].data_ptr(),
+                                                         ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
+                   "n2v_edge_logreg_loss_grad")
+    return out
+
+
+def edge_loss_grad(X: torch.Tensor, a, b, y, w, b0, op: str = "hadamard",
+                   workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(loss float64 [1], gw float64 [dim], gb float64 [1]), device tensors: the summed logistic loss of every pair's
+    score against its label y (nonzero: an edge) and its gradient by (w, b0) -- unregularised sums, one pass over the
+    pairs, no feature matrix (n2v_edge_logreg_loss_grad)"""
+    code = _operator(op)
+    X = _dense.matrix(X)
+    a, b = _pairs(a, b, X.shape[0], X.device)
+    out = _edge_loss_grad_flat(X, a, b, _labels(y, a.shape[0], X.device), w, b0, code, workspace)
+    dim = X.shape[1]
+    return out[:1], out[1:1 + dim], out[1 + dim:]
+
+
+def fit_edges(X: torch.Tensor, a, b, y, op: str = "hadamard", C: float = 1.0, max_iter: int = 100, tol: float = 1e-4,
+              history: int = 10, loss_grad_fn: Optional[Callable] = None) -> EdgeClassifier:
+    """The paper's link-prediction classifier: L2 logistic regression on the edge feature op(x_a, x_b) of the pairs
+    (a[i], b[i]) with labels y (nonzero: an edge), from w = 0, b = 0.  Minimises sum of the logistic losses +
+    |w|^2 / (2 C) (the bias is not penalised) with classify.lbfgs, as classify.fit does for one class: the same
+    stopping rule (max |grad| / n_pairs <= tol), the same reasons.  One evaluation is one pass over the pairs and one
+    synchronisation; no [n_pairs, dim] matrix is made.  An index outside [0, n) is an IndexError before any launch, a
+    non-finite value in X a ValueError.  loss_grad_fn(w [1, dim], b [1]) -> (loss, gw, gb) replaces the kernel (host
+    tensors in and out), for tests."""
+    from node2vec_amd import classify
+
+    code = _operator(op)
+    n, dim = _dense.shape(X)
+    if not float(C) > 0.0 or int(max_iter) < 1 or not float(tol) >= 0.0 or int(history) < 1:
+        raise ValueError("C must be > 0, max_iter and history >= 1, tol >= 0")
+    if loss_grad_fn is None:
+        X = _dense.matrix(X)
+    a, b = _pairs(a, b, n, X.device)
+    n_pairs = int(a.shape[0])
+    if n_pairs < 1:
+        raise ValueError("fit_edges needs at least one pair")
+    y = _labels(y, n_pairs, X.device)
+    if not bool(torch.isfinite(torch.stack(torch.aminmax(X))).all()):  # NaN propagates; no [n, dim] temporary
+        raise ValueError("X holds a non-finite value")
+    if loss_grad_fn is None:
+        ws = alloc_edge_workspace(n_pairs, dim, X.device)
+
+        def loss_grad_fn(w, b0):  # host parameters in, host sums out: the copy back is the one synchronisation
+            flat = _edge_loss_grad_flat(X, a, b, y, w.reshape(dim), b0, code, ws).cpu()
+            return flat[:1], flat[1:1 + dim], flat[1 + dim:]
+    theta, f, gmax, n_iter, n_evals, reason = classify.lbfgs(
+        classify.regularised(loss_grad_fn, 1, dim, 1.0 / float(C)), (1, dim + 1), n_pairs, max_iter, tol, history)
+    dev = X.device
+    return EdgeClassifier(theta[0, :dim].contiguous().to(dev), theta[0, dim:].contiguous().to(dev), op, f, gmax,
+                          n_iter, n_evals, reason == "gradient", reason)
+
+
+def link_classifier_auc(graph, wv, n_pairs: int, seed: int, op: str = "hadamard", train_fraction: float = 0.5,
+                        center: bool = True, **fit_kw) -> Dict[str, object]:
+    """The paper's link-prediction protocol on the vectors `wv` (a KeyedVectors whose tokens are vertex ids): n_pairs
+    edges (sample_edges, seed) against n_pairs non-edges (sample_non_edges, seed + 1), as link_auc draws them; pairs
+    with a vertex outside the vocabulary are dropped and counted; the rest are split by classify.split_rows(.,
+    train_fraction, seed); fit_edges (whose other arguments pass through) on the training pairs; the exact auc of
+    edge_scores on the held-out pairs (NaN when they lack a class).  center: the column mean is subtracted from the
+    vectors first, as in link_auc.  The edges are sampled from `graph` as it is -- the graph the vectors were trained
+    on, unless the caller removed the test edges before training, which is the caller's job as it is for link_auc.
+    -> {"auc", "train_pairs", "test_pairs", "dropped", "result"}"""
+    from node2vec_amd import classify
+
+    _operator(op)
+    if not 0.0 < float(train_fraction) <= 1.0:
+        raise ValueError("train_fraction must be in (0, 1]")
+    X = wv._device_vectors()
+    if center:
+        X = X - X.mean(dim=0, keepdim=True)
+    rows_a, rows_b, labels, dropped = [], [], [], 0
+    for label, (a, b) in ((1, sample_edges(graph, n_pairs, seed)), (0, sample_non_edges(graph, n_pairs, seed + 1))):
+        ra, rb = _rows_of(wv, a.to(X.device)), _rows_of(wv, b.to(X.device))
+        keep = (ra >= 0) & (rb >= 0)
+        dropped += int((~keep).sum())
+        rows_a.append(ra[keep])
+        rows_b.append(rb[keep])
+        labels.append(torch.full((int(keep.sum()),), label, dtype=torch.uint8, device=X.device))
+    ra, rb, y = torch.cat(rows_a), torch.cat(rows_b), torch.cat(labels)
+    train, test = classify.split_rows(int(y.shape[0]), train_fraction, seed)
+    tr, te = torch.from_numpy(train).to(X.device), torch.from_numpy(test).to(X.device)
+    result = fit_edges(X, ra[tr], rb[tr], y[tr], op=op, **fit_kw)
+    z = edge_scores(X, ra[te], rb[te], result.w, result.b, op)
+    pos, neg = z[y[te] != 0], z[y[te] == 0]
+    value = auc(pos, neg) if pos.numel() and neg.numel() else float("nan")
+    return {"auc": value, "train_pairs": int(len(train)), "test_pairs": int(len(test)), "dropped": dropped,
+            "result": result}
