@@ -1197,6 +1197,33 @@ int n2v_tsne_step(const int64_t *rowptr, const int32_t *col, const float *val, i
                   float momentum, float min_gain, float *vel, float *gain, float *Y_next, float *grad_out,
                   void *stream);
 
+/* Filtered link-prediction ranks over trained vectors (csrc/n2v_linkrank.hip, DESIGN.md "Link ranking"): where the
+ * held-out endpoint of an edge stands among ALL rows, the statistic behind filtered MRR, mean rank and Hits@K.
+ * ADDITIONS ONLY: N2V_ABI_VERSION stays 15.  X, inv_norm as for n2v_knn_* (the dot product: inv_norm all ones); a, b:
+ * [n_queries] int64 row numbers (u_q, v_q), 0 <= n_queries < 2^31.  With s(u, w) the score n2v_knn_scores gives query
+ * row u against row w, bit for bit, thr_q = s(u_q, v_q) and F(u) the distinct columns of row u of the filter CSR
+ * (rowptr int64 [n + 1], col int32, ascending within a row, multi-edges adjacent, empty rows allowed; both NULL: no
+ * filter):
+ *   counts_out[q, 0] = #{ w in [0, n) : w != u_q, w != v_q, w not in F(u_q), s(u_q, w) >  thr_q }
+ *   counts_out[q, 1] = the same with ==
+ * A NaN on either side counts in neither: a NaN thr_q gives (0, 0).  thr_out: [n_queries] fp32 or NULL.  The
+ * [n_queries, n] score matrix is never written: a scan over (query tile, chunk of rows) counts every row in integers
+ * (integer atomic adds, no float atomics), then a pass over the lists {u, v} + F(u) takes their comparisons away again
+ * with the same bits.  Argument errors are N2V_EINVAL before anything is launched (sizes, exactly one of rowptr / col,
+ * NULL pointers, a workspace that is NULL, not 16-byte aligned or smaller than n2v_link_rank_workspace_bytes);
+ * n_queries == 0 or n == 0 is N2V_OK and launches nothing.  a, b and col are device memory, which the host cannot
+ * read without a synchronisation: a query with a row outside [0, n) is never dereferenced and answers thr NaN,
+ * counts (0, 0) (callers check the rows where they are made, as for n2v_knn_*' query_rows); a column outside [0, n)
+ * is skipped. */
+/* Bytes of workspace n2v_link_rank needs (q_hat, the thresholds, the checked rows); -1 for sizes it refuses. */
+int64_t n2v_link_rank_workspace_bytes(int64_t n, int32_t dim, int64_t n_queries);
+/* The scan's launch shape for these sizes: chunks of *chunk_rows_out rows (a multiple of 128), *n_chunks_out of them,
+ * the last one ragged. */
+int n2v_link_rank_plan(int64_t n, int32_t dim, int64_t n_queries, int64_t *chunk_rows_out, int32_t *n_chunks_out);
+int n2v_link_rank(const float *X, const float *inv_norm, int64_t n, int32_t dim, const int64_t *a, const int64_t *b,
+                  int64_t n_queries, const int64_t *rowptr, const int32_t *col, float *thr_out, int64_t *counts_out,
+                  void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,7 +42,8 @@ SYMBOLS = ("n2v_abi_version", "n2v_status_string", "n2v_device_count", "n2v_alia
            "n2v_pca_workspace_bytes", "n2v_pca_mean", "n2v_pca_scatter", "n2v_ivf_workspace_bytes", "n2v_ivf_plan",
            "n2v_ivf_topk", "n2v_silhouette_workspace_bytes", "n2v_silhouette", "n2v_tsne_plan",
            "n2v_tsne_workspace_bytes", "n2v_tsne_repulse", "n2v_tsne_step", "n2v_ivfpq_workspace_bytes",
-           "n2v_ivfpq_plan", "n2v_ivfpq_lut", "n2v_ivfpq_topk")
+           "n2v_ivfpq_plan", "n2v_ivfpq_lut", "n2v_ivfpq_topk", "n2v_link_rank_workspace_bytes",
+           "n2v_link_rank_plan", "n2v_link_rank")
 
 
 class WeightedHubs(C.Structure):
@@ -341,6 +342,14 @@ def load():
                                  C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                  C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_int64, C.c_void_p]
+    L.n2v_link_rank_workspace_bytes.restype = C.c_int64
+    L.n2v_link_rank_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64]
+    L.n2v_link_rank_plan.restype = C.c_int
+    L.n2v_link_rank_plan.argtypes = L.n2v_link_rank_workspace_bytes.argtypes + [C.POINTER(C.c_int64),
+                                                                                C.POINTER(C.c_int32)]
+    L.n2v_link_rank.restype = C.c_int
+    L.n2v_link_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     _lib = L
     return L
 

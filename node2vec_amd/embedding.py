@@ -401,6 +401,24 @@ class KeyedVectors:
         return linkpred.edge_scores(self._device_vectors(), torch.from_numpy(ra), torch.from_numpy(rb), result.w,
                                     result.b, result.op).cpu().numpy()
 
+    def target_ranks(self, tokens_a, tokens_b, graph=None, metric: str = "cosine"):
+        """where tokens_b[i] stands among the whole vocabulary as a partner of tokens_a[i]: (greater, equal int64 [n],
+        thr fp32 [n]) -- how many tokens score above, and equal to, tokens_b[i] against tokens_a[i], and that score
+        (linkpred.target_ranks; csrc/n2v_linkrank.hip: no [n, vocabulary] score matrix is made).  graph: a DeviceGraph
+        over vertex ids, for tokens that are vertex ids: the neighbours tokens_a[i] has in it are not candidates."""
+        from node2vec_amd import linkpred
+
+        if metric not in linkpred.METRICS:
+            raise ValueError(f"metric {metric!r}: " + " | ".join(linkpred.METRICS))
+        ra, rb = self._pair_rows(tokens_a, tokens_b)
+        X = self._device_vectors()
+        if metric == "cosine":
+            self.init_sims()
+        filt = None if graph is None else linkpred.rows_graph(graph.to(X.device), self)
+        greater, equal, thr = linkpred.target_ranks(X, torch.from_numpy(ra), torch.from_numpy(rb), graph=filt,
+                                                    metric=metric, inv_norm=self._inv_norm)
+        return greater.cpu().numpy(), equal.cpu().numpy(), thr.cpu().numpy()
+
     def kmeans(self, k: int, metric: str = "cosine", restrict_vocab: Optional[int] = None, **kw):
         """k-means of the vectors on the GPU (node2vec_amd.cluster.kmeans, whose other arguments pass through):
         a KMeansResult whose labels[i] is the cluster of row i (token index2word[i]).  The default metric is
@@ -624,6 +642,26 @@ class _ModelQueries:
         if result is None:
             raise ValueError("No classifier is available. Please run link_classifier()")
         return pd.DataFrame({"src": src, "dst": dst, "score": self.model.wv.edge_scores(src, dst, result)})
+
+    def link_ranking(self, df_test_edges: pd.DataFrame, df_train_edges: Optional[pd.DataFrame] = None,
+                     ks=(1, 10, 50, 100), metric: str = "cosine", both: bool = True) -> pd.DataFrame:
+        """One row ["mrr", "mean_rank", "hits@k" for every k of ks, "n", "dropped"]: the filtered ranking of the
+        held-out edges of df_test_edges (["src", "dst"], vertex ids) among every vocabulary vertex
+        (linkpred.link_ranking: with `both`, dst among the partners of src and src among those of dst).
+        df_train_edges (["src", "dst"], the arcs as stored: both directions of an undirected edge): the graph the
+        vectors were trained on, whose edges are not candidates; None: nothing is filtered.  A test vertex outside the
+        vocabulary is dropped and counted."""
+        from node2vec_amd import linkpred
+        from node2vec_amd.graph import DeviceGraph
+
+        wv = self._wv()
+        src, dst = self._edge_ids(df_test_edges)
+        train = None
+        if df_train_edges is not None:
+            tsrc, tdst = self._edge_ids(df_train_edges)
+            train = DeviceGraph.from_edges(tsrc, tdst, device=wv._device_vectors().device)
+        out = linkpred.link_ranking(train, wv, src, dst, ks=ks, metric=metric, both=both)
+        return pd.DataFrame([out])
 
     def cluster(self, k: int, metric: str = "cosine", **kw) -> pd.DataFrame:
         """["id" | "name", "cluster"]: the k-means cluster of every vocabulary vertex, in vocabulary order

@@ -13,10 +13,16 @@ feature in registers and accumulates the loss and gradient in one fixed order --
 (DESIGN.md "Link-prediction classifier").  edge_scores() scores pairs with the fitted weights, link_classifier_auc()
 runs the whole protocol.
 
-Device tensors in and out.  There is no CPU path for the kernels: a missing GPU or library raises.  auc() is
-plain torch and works on CPU tensors too.
+Ranks against EVERY candidate (csrc/n2v_linkrank.hip, DESIGN.md "Link ranking"): holdout_edges() takes a seeded share
+of the edges out of a graph before training, target_ranks() counts for every held-out pair (u, v) the rows that score
+above, and equal to, v against u once u's known neighbours are left out -- fused, so that no [queries, n] score
+matrix exists -- ranking_metrics() turns the counts into filtered MRR, mean rank and Hits@K, and link_ranking() runs
+the three on a KeyedVectors.
+
+Device tensors in and out.  There is no CPU path for the kernels: a missing GPU or library raises.  auc(),
+ranking_metrics() and holdout_edges() are plain torch and work on CPU tensors too.
 """
-from typing import Callable, Dict, NamedTuple, Optional, Tuple
+from typing import Callable, Dict, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -26,6 +32,7 @@ from node2vec_amd import _dense, _lib
 METRICS = {"dot": _lib.PAIR_DOT, "cosine": _lib.PAIR_COSINE}
 OPERATORS = {"average": _lib.PAIR_AVERAGE, "hadamard": _lib.PAIR_HADAMARD, "l1": _lib.PAIR_L1, "l2": _lib.PAIR_L2}
 NON_EDGE_ROUNDS = 32  # sample_non_edges gives up after this many rounds of redrawing
+TIE_RULES = ("mean", "optimistic", "pessimistic")
 
 
 def _pairs(a, b, n: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -357,3 +364,186 @@ def link_classifier_auc(graph, wv, n_pairs: int, seed: int, op: str = "hadamard"
     value = auc(pos, neg) if pos.numel() and neg.numel() else float("nan")
     return {"auc": value, "train_pairs": int(len(train)), "test_pairs": int(len(test)), "dropped": dropped,
             "result": result}
+
+
+def link_rank_plan(n: int, dim: int, n_queries: int) -> Tuple[int, int]:
+    """(chunk_rows, n_chunks) of target_ranks' scan for one launch of these sizes (n2v_link_rank_plan)"""
+    import ctypes
+
+    rows, chunks = ctypes.c_int64(), ctypes.c_int32()
+    _lib.check(_lib.load().n2v_link_rank_plan(n, dim, n_queries, ctypes.byref(rows), ctypes.byref(chunks)),
+               "n2v_link_rank_plan")
+    return int(rows.value), int(chunks.value)
+
+
+def target_ranks(X: torch.Tensor, a, b, graph=None, metric: str = "cosine",
+                 inv_norm: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Where row b[i] stands among ALL rows of X as a partner of row a[i]: (greater, equal int64 [n_pairs], thr fp32
+    [n_pairs]).  With s(u, w) the score similarity.scores gives query row u against row w, bit for bit ("dot": the
+    same with every inverse norm 1), thr = s(a[i], b[i]) and, over the rows w other than a[i], b[i] and the columns
+    of row a[i] of `graph` (a CSR over the rows of X -- the known edges, multi-edges once; None: no filter),
+    greater = #{s(a[i], w) > thr} and equal = #{s(a[i], w) == thr}.  A NaN counts on neither side: a NaN thr gives
+    (0, 0).  One scan of X per batch of queries, the counts kept in registers: nothing of size n_pairs x n is stored
+    (n2v_link_rank).  The queries go in equal batches whose workspace stays under similarity.WORKSPACE_LIMIT; the
+    result does not depend on the batches.  An index outside [0, n) is an IndexError before any launch."""
+    from node2vec_amd import similarity
+
+    if metric not in METRICS:
+        raise ValueError(f"metric {metric!r}: " + " | ".join(METRICS))
+    X = _dense.matrix(X)
+    n, dim = X.shape
+    a, b = _pairs(a, b, n, X.device)
+    nq = int(a.shape[0])
+    rowptr = col = None
+    if graph is not None:
+        rowptr, col, nv = _graph_arrays(graph)
+        if nv != n or rowptr.device != X.device:
+            raise ValueError(f"the filter graph must have one vertex per row of X ({n}) on {X.device}, "
+                             f"not {nv} on {rowptr.device}")
+        if col.numel() == 0:
+            rowptr = col = None
+    counts = torch.zeros((nq, 2), dtype=torch.int64, device=X.device)
+    thr = torch.full((nq,), float("nan"), dtype=torch.float32, device=X.device)
+    if nq == 0:
+        return counts[:, 0].contiguous(), counts[:, 1].contiguous(), thr
+    if metric == "cosine":
+        norms = _dense.norms(X, inv_norm)
+    else:
+        norms = torch.ones(n, dtype=torch.float32, device=X.device)
+    L = _lib.load()
+    step = nq
+    while step > 1 and L.n2v_link_rank_workspace_bytes(n, dim, step) > similarity.WORKSPACE_LIMIT:
+        step = (step + 1) // 2
+    with torch.cuda.device(X.device):
+        for i in range(0, nq, step):
+            j = min(nq, i + step)
+            ws = _dense.workspace(L.n2v_link_rank_workspace_bytes, n, dim, j - i, device=X.device)
+            _lib.check(L.n2v_link_rank(X.data_ptr(), norms.data_ptr(), n, dim, a[i:j].data_ptr(), b[i:j].data_ptr(),
+                                       j - i, _dense.ptr(rowptr), _dense.ptr(col), thr[i:j].data_ptr(),
+                                       counts[i:j].data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
+                       "n2v_link_rank")
+    return counts[:, 0].contiguous(), counts[:, 1].contiguous(), thr
+
+
+def ranking_metrics(greater, equal, ks: Sequence[int] = (1, 10, 50, 100), tie: str = "mean") -> Dict[str, float]:
+    """{"mrr", "mean_rank", "hits@k" for every k of ks, "n"} of target_ranks' counts.  The rank of a query is
+    1 + greater + equal / 2 ("mean": the expected place among its ties), 1 + greater ("optimistic") or
+    1 + greater + equal ("pessimistic"); mrr is the mean of 1 / rank, hits@k the share of ranks <= k.  Float64 on the
+    host, from the integers.  No query: ValueError."""
+    if tie not in TIE_RULES:
+        raise ValueError(f"tie {tie!r}: " + " | ".join(TIE_RULES))
+    ks = [int(k) for k in ks]
+    if any(k < 1 for k in ks):
+        raise ValueError("every k must be >= 1")
+    g = torch.as_tensor(greater).reshape(-1).cpu().to(torch.float64)
+    e = torch.as_tensor(equal).reshape(-1).cpu().to(torch.float64)
+    if g.shape[0] != e.shape[0]:
+        raise ValueError(f"greater and equal must have the same length, not {g.shape[0]} and {e.shape[0]}")
+    if g.numel() == 0:
+        raise ValueError("ranking metrics of no query")
+    if bool((g < 0).any()) or bool((e < 0).any()):
+        raise ValueError("counts must be >= 0")
+    rank = 1.0 + g + {"mean": 0.5, "optimistic": 0.0, "pessimistic": 1.0}[tie] * e
+    out = {"mrr": float((1.0 / rank).mean()), "mean_rank": float(rank.mean())}
+    for k in ks:
+        out[f"hits@{k}"] = float((rank <= k).to(torch.float64).mean())
+    out["n"] = int(g.numel())
+    return out
+
+
+def _member(sorted_keys: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
+    """bool: keys[i] is among sorted_keys (ascending)"""
+    if sorted_keys.numel() == 0:
+        return torch.zeros_like(keys, dtype=torch.bool)
+    k = torch.searchsorted(sorted_keys, keys).clamp(max=sorted_keys.numel() - 1)
+    return sorted_keys[k] == keys
+
+
+def holdout_edges(graph, fraction: float, seed: int, undirected: bool = True):
+    """(train_graph, test_a, test_b): `graph` without a seeded sample of its edges, and the edges taken (int64).
+
+    undirected: an edge is the unordered pair {a, b}; both arcs (every copy of them) leave together and the pair is
+    reported once, with a < b.  Otherwise an edge is the arc a -> b (every copy of it).  Self-loops are never taken.
+    The distinct edges are put in one seeded order (a permutation drawn on the host, so the split is a function of
+    (graph, fraction, seed) alone); an edge may leave unless it is, in that order, the last edge with an arc out of
+    one of its endpoints, and the first round(fraction * edges) that may leave do.  So every vertex that had an
+    out-edge keeps one -- its degree stays >= 1, which every walk needs -- but the graph may still fall apart:
+    connectivity is not kept.  Where few edges may leave (a star: none) fewer are returned than asked for.  Weights
+    stay with the arcs that remain.  Plain torch, on the graph's device (host tensors work too)."""
+    from node2vec_amd.graph import DeviceGraph
+
+    fraction = float(fraction)
+    if not 0.0 <= fraction < 1.0:
+        raise ValueError("fraction must be in [0, 1)")
+    rowptr, col, nv = graph.rowptr, graph.col, graph.n_vertices
+    dev = rowptr.device
+    src = torch.repeat_interleave(torch.arange(nv, dtype=torch.int64, device=dev), graph.degrees())
+    dst = col.to(torch.int64)
+    scale = max(nv, 1)
+    if undirected:
+        key = torch.minimum(src, dst) * scale + torch.maximum(src, dst)
+    else:
+        key = src * scale + dst
+    edges = torch.unique(key[src != dst])  # ascending: the order the permutation is laid over
+    ea, eb = edges // scale, edges % scale
+    n_edges = int(edges.numel())
+    perm = torch.randperm(n_edges, generator=torch.Generator().manual_seed(int(seed))).to(dev)
+    place = torch.empty(n_edges, dtype=torch.int64, device=dev)
+    place[perm] = torch.arange(n_edges, dtype=torch.int64, device=dev)
+    if undirected:
+        arcs = torch.unique(src * scale + dst)
+        out_a, out_b = _member(arcs, ea * scale + eb), _member(arcs, eb * scale + ea)
+    else:
+        out_a, out_b = torch.ones_like(ea, dtype=torch.bool), torch.zeros_like(ea, dtype=torch.bool)
+    last = torch.full((max(nv, 1),), -1, dtype=torch.int64, device=dev)  # place of each vertex's last out-edge
+    last.scatter_reduce_(0, ea[out_a], place[out_a], "amax")
+    last.scatter_reduce_(0, eb[out_b], place[out_b], "amax")
+    may_leave = ~((out_a & (last[ea] == place)) | (out_b & (last[eb] == place))) if n_edges else out_a
+    in_order = perm[may_leave[perm]]
+    taken = in_order[:int(round(fraction * n_edges))]
+    keep = ~_member(torch.sort(edges[taken]).values, key)
+    train_rowptr = torch.zeros(nv + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(src[keep], minlength=nv), 0, out=train_rowptr[1:])
+    train = DeviceGraph(train_rowptr, col[keep], None if graph.unit_weights else graph.w[keep])
+    return train, ea[taken], eb[taken]
+
+
+def rows_graph(graph, wv):
+    """`graph` (over vertex ids) as a unit-weight CSR over the rows of wv's vocabulary, on the graph's device: the
+    filter target_ranks wants.  Arcs with a vertex outside the vocabulary are left out."""
+    from node2vec_amd.graph import DeviceGraph
+
+    rowptr, col, nv = _graph_arrays(graph)
+    rows = _rows_of(wv, torch.arange(nv, dtype=torch.int64, device=rowptr.device))
+    src = torch.repeat_interleave(rows, graph.degrees())
+    dst = rows[col.to(torch.int64)]
+    keep = (src >= 0) & (dst >= 0)
+    return DeviceGraph.from_edges(src[keep], dst[keep], None, n_vertices=len(wv), device=rowptr.device)
+
+
+def link_ranking(train_graph, wv, test_a, test_b, ks: Sequence[int] = (1, 10, 50, 100), metric: str = "cosine",
+                 both: bool = True, tie: str = "mean") -> Dict[str, float]:
+    """Filtered ranking of held-out edges (test_a[i], test_b[i]) (vertex ids, as holdout_edges returns them) under
+    the vectors `wv` (a KeyedVectors whose tokens are vertex ids): test_b[i] is ranked among every vocabulary vertex
+    as a partner of test_a[i], the neighbours test_a[i] has in `train_graph` left out (target_ranks) -- and, with
+    `both`, test_a[i] among the partners of test_b[i] as well, the two pooled.  Pairs with a vertex outside the
+    vocabulary are dropped and counted.  -> ranking_metrics' dict (n: the ranked queries) and "dropped"."""
+    X = wv._device_vectors()
+    inv_norm = None
+    if metric == "cosine":
+        wv.init_sims()
+        inv_norm = wv._inv_norm
+    ra = _rows_of(wv, torch.as_tensor(test_a).to(device=X.device, dtype=torch.int64).reshape(-1))
+    rb = _rows_of(wv, torch.as_tensor(test_b).to(device=X.device, dtype=torch.int64).reshape(-1))
+    if ra.shape[0] != rb.shape[0]:
+        raise ValueError(f"test_a and test_b must have the same length, not {ra.shape[0]} and {rb.shape[0]}")
+    known = (ra >= 0) & (rb >= 0)
+    dropped = int((~known).sum())
+    ra, rb = ra[known], rb[known]
+    if both:
+        ra, rb = torch.cat((ra, rb)), torch.cat((rb, ra))
+    filt = None if train_graph is None else rows_graph(train_graph.to(X.device), wv)
+    greater, equal, _ = target_ranks(X, ra, rb, graph=filt, metric=metric, inv_norm=inv_norm)
+    out = ranking_metrics(greater, equal, ks, tie)
+    out["dropped"] = dropped
+    return out
