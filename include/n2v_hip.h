@@ -1224,6 +1224,47 @@ int n2v_link_rank(const float *X, const float *inv_norm, int64_t n, int32_t dim,
                   int64_t n_queries, const int64_t *rowptr, const int32_t *col, float *thr_out, int64_t *counts_out,
                   void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Fold-in: rows for NEW vertices against a frozen skip-gram negative-sampling model (csrc/n2v_foldin.hip, DESIGN.md
+ * "Fold-in").  ADDITIONS ONLY: N2V_ABI_VERSION stays 15.  walks: [n_walks, walk_len] int32, walk_len <=
+ * N2V_SGNS_MAX_SENTENCE, n_walks < 2^31; a token in [0, n_vocab) is a known word, one in [n_vocab, n_vocab + n_new) is
+ * new vertex tok - n_vocab, any other is dropped.  params: n_vocab, sentence_base, seed, dim, window, negative, alpha,
+ * cum_index(_bits), row_alpha and max_waves as for n2v_sgns_train; deterministic is not read (the result is the same
+ * bits on any launch geometry); batched and window_cache must be 0.  Sentence preparation is n2v_sgns_train's, but
+ * a new token is always kept (sample_int has no entry for it).  A pair (centre position i, context position j) of
+ * n2v_sgns_train is TRAINABLE when sent[j] is new and sent[i] is known; it is trained as there, on the new vertex's row,
+ * with the same negative draws, and without the updates of syn1neg.  Everything but new_rows is only read.
+ *
+ * A record names one trainable pair; the pairs of one new vertex are trained in (row, i, j) ascending order. */
+typedef struct n2v_foldin_record {
+  int32_t vertex; /* the new index, tok - n_vocab */
+  int32_t row;    /* the walk: the sentence is sentence_base + row */
+  int32_t pos;    /* i | rel << 16: the centre's position in the prepared sentence, and the window slot
+                     rel = j - i + window - (j > i) */
+  int32_t centre; /* the known word sent[i] */
+} n2v_foldin_record;
+
+/* The pair listing, in two passes with the caller's exclusive prefix sum over rows in between:
+ * row_count_out[r] = trainable pairs of walk r; then records_out[row_off[r] ...] = those pairs in (i, j) order, so that
+ * the records stand in (row, i, j) order and no atomic decides an order.  Argument errors (whatever n2v_sgns_train
+ * refuses, n_new < 0, n_vocab + n_new past the int32 tokens, NULL pointers) are N2V_EINVAL before anything is launched;
+ * n_walks == 0 is N2V_OK. */
+int n2v_foldin_pair_counts(const int32_t *walks, int64_t n_walks, int32_t walk_len, int64_t n_new,
+                           const uint32_t *sample_int, const n2v_sgns_params *params_host, int64_t *row_count_out,
+                           void *stream);
+int n2v_foldin_pair_records(const int32_t *walks, int64_t n_walks, int32_t walk_len, int64_t n_new,
+                            const uint32_t *sample_int, const n2v_sgns_params *params_host, const int64_t *row_off,
+                            n2v_foldin_record *records_out, void *stream);
+
+/* One pass (epoch) of chain training, one wave per new vertex.  records: the listing's, grouped by vertex with a STABLE
+ * sort (the order inside a vertex stays (row, i, j)); vertex_off: int64 [n_new + 1], vertex u owns records
+ * [vertex_off[u], vertex_off[u + 1]); new_rows: fp32 [n_new, dim], in place -- a vertex without records keeps its row.
+ * params, n_walks and walk_len as for the listing that made the records (the draws are keyed on them).  A record whose
+ * row, position or centre lies outside them is not trained.  Argument errors as above, a NULL new_rows with
+ * n_new > 0 included, are N2V_EINVAL before anything is launched; n_new == 0 or n_walks == 0 is N2V_OK. */
+int n2v_foldin_train(const n2v_foldin_record *records, const int64_t *vertex_off, int64_t n_new, int64_t n_walks,
+                     int32_t walk_len, float *new_rows, const float *syn1neg, const uint32_t *cum_table,
+                     const float *exp_table, const n2v_sgns_params *params_host, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,7 +43,8 @@ SYMBOLS = ("n2v_abi_version", "n2v_status_string", "n2v_device_count", "n2v_alia
            "n2v_ivf_topk", "n2v_silhouette_workspace_bytes", "n2v_silhouette", "n2v_tsne_plan",
            "n2v_tsne_workspace_bytes", "n2v_tsne_repulse", "n2v_tsne_step", "n2v_ivfpq_workspace_bytes",
            "n2v_ivfpq_plan", "n2v_ivfpq_lut", "n2v_ivfpq_topk", "n2v_link_rank_workspace_bytes",
-           "n2v_link_rank_plan", "n2v_link_rank")
+           "n2v_link_rank_plan", "n2v_link_rank", "n2v_foldin_pair_counts", "n2v_foldin_pair_records",
+           "n2v_foldin_train")
 
 
 class WeightedHubs(C.Structure):
@@ -350,6 +351,15 @@ def load():
     L.n2v_link_rank.restype = C.c_int
     L.n2v_link_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.n2v_foldin_pair_counts.restype = C.c_int
+    L.n2v_foldin_pair_counts.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(SgnsParams),
+                                         C.c_void_p, C.c_void_p]
+    L.n2v_foldin_pair_records.restype = C.c_int
+    L.n2v_foldin_pair_records.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,
+                                          C.POINTER(SgnsParams), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.n2v_foldin_train.restype = C.c_int
+    L.n2v_foldin_train.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.POINTER(SgnsParams), C.c_void_p]
     _lib = L
     return L
 

@@ -508,6 +508,31 @@ class KeyedVectors:
         X, inv_norm = self._window(restrict_vocab, True)
         return tsne.fit(X, perplexity=perplexity, inv_norm=inv_norm, **kw)
 
+    def with_rows(self, tokens, rows) -> "KeyedVectors":
+        """A new KeyedVectors holding this one's rows followed by `rows` [m, dim] under `tokens` (m vertex ids or
+        strings: the vertices Node2VecHIP.infer_vertices folded in), so that most_similar, build_index, kmeans and
+        the rest run on the extended set.  This object is untouched and shares no memory with the result."""
+        if isinstance(tokens, torch.Tensor):
+            tokens = tokens.cpu().numpy()
+        tokens = np.asarray(tokens) if not isinstance(tokens, np.ndarray) else tokens
+        if rows.ndim != 2 or rows.shape[0] != tokens.shape[0] or int(rows.shape[1]) != self.vector_size:
+            raise ValueError(f"with_rows wants {tokens.shape[0]} rows of {self.vector_size} values, "
+                             f"not {tuple(rows.shape)}")
+        if self.ids is not None and tokens.dtype.kind in "iu":
+            names = np.concatenate([self.ids, tokens.astype(np.int64)])
+        else:
+            names = list(self.index2word) + [str(t) for t in tokens.tolist()]
+        if len(set(names.tolist() if isinstance(names, np.ndarray) else names)) != len(names):
+            raise ValueError("with_rows: a token is already in the vocabulary, or is given twice")
+        old = self._vectors
+        if isinstance(old, torch.Tensor):
+            new = rows if isinstance(rows, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(rows))
+            vectors = torch.cat([old, new.to(device=old.device, dtype=old.dtype)], 0)
+        else:
+            new = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+            vectors = np.concatenate([old, new.astype(old.dtype, copy=False)], 0)
+        return KeyedVectors(names, vectors)
+
     @classmethod
     def load_word2vec_format(cls, fname: str) -> "KeyedVectors":
         with open(fname) as f:
@@ -770,19 +795,20 @@ class Node2VecHIP(Node2VecBase, _ModelQueries):
         self.w2v_params = w2v_params
 
     # -- training ---------------------------------------------------------------
-    def _walk_tensor(self, device) -> torch.Tensor:
-        if isinstance(self.walks, torch.Tensor):
-            return self.walks.to(device=device, dtype=torch.int32)
+    def _walk_tensor(self, device, walks=None) -> torch.Tensor:
+        walks = self.walks if walks is None else walks
+        if isinstance(walks, torch.Tensor):
+            return walks.to(device=device, dtype=torch.int32)
         from node2vec_amd import corpus
 
-        dev_walks = corpus.lookup(self.walks)  # the frame random_walk() returned, unchanged
+        dev_walks = corpus.lookup(walks)  # the frame random_walk() returned, unchanged
         if dev_walks is not None:
             return dev_walks.to(device=device, dtype=torch.int32)
-        arr = corpus.arrow_rows(self.walks["walk"])  # an Arrow-backed column: no Python object per vertex
+        arr = corpus.arrow_rows(walks["walk"])  # an Arrow-backed column: no Python object per vertex
         if arr is not None:
             return torch.from_numpy(np.array(arr, dtype=np.int32)).to(device)  # (a copy: the Arrow buffer is read-only)
         # embedding.py:125 requires equal-length walks (np.array(walks.tolist()))
-        arr = np.array(self.walks["walk"].tolist())
+        arr = np.array(walks["walk"].tolist())
         if arr.ndim != 2:
             raise ValueError("walks must all have the same length")
         return torch.from_numpy(arr.astype(np.int32)).to(device)
@@ -849,6 +875,60 @@ class Node2VecHIP(Node2VecBase, _ModelQueries):
         # host copies would be 2 x 51 GB + 10^8 Python strings that most callers never read
         self.model = HipW2V(KeyedVectors(vocab.ids, m.syn0), m.syn1neg, p, int(m.pairs.item()))
         return self.model
+
+    # -- fold-in: vertices the model has never seen ---------------------------------
+    def infer_vertices(self, df_walks_or_tensor, epochs: Optional[int] = None, init=None) -> pd.DataFrame:
+        """Embeds the vertices of `df_walks_or_tensor` (walks over the grown graph, as fit() takes them) that are
+        not in model.wv, against the fitted model, which stays exactly as it is (node2vec_amd/foldin.py, DESIGN.md
+        "Fold-in").  The new vertices are numbered in ascending id.  Returns a DataFrame ["id" | "name", "vector"]
+        shaped like embedding(); model.wv.with_rows(ids, vectors) gives a KeyedVectors over old and new.
+
+        The negative table is rebuilt from the walks this object was fitted on (the fitted model keeps no counts):
+        RuntimeError if they no longer give the model's vocabulary.  epochs: default w2v_params["iter"]; init:
+        the starting rows [n_new, dim], default seeded.  Skip-gram negative sampling only: ValueError for a model
+        fitted with sg=0 or batched=True."""
+        from types import SimpleNamespace
+
+        from node2vec_amd import _lib, foldin
+
+        wv = self._wv()
+        p = self.model.params
+        if not p.get("sg", 1) or p.get("batched", False):
+            raise ValueError("infer_vertices is defined for skip-gram negative sampling only (sg=1, not batched)")
+        dev = _lib.require_gpu()
+        vocab = sgns.build_vocab(self._walk_tensor(dev), int(p["min_count"]))
+        if wv.ids is None or not np.array_equal(vocab.ids.cpu().numpy(), wv.ids):
+            raise RuntimeError("the walks of this object do not give the vocabulary of its model: infer_vertices "
+                               "rebuilds the negative-sampling table from the walks the model was fitted on")
+        n_vocab = len(vocab)
+        walks = self._walk_tensor(dev, df_walks_or_tensor).long()
+        seen = torch.unique(walks[walks >= 0])  # ascending
+        inside = seen < vocab.index_of.numel()
+        known = torch.zeros_like(inside)
+        known[inside] = vocab.index_of[seen[inside]] >= 0
+        new_ids = seen[~known]
+        n_new = int(new_ids.numel())
+        if n_vocab + n_new > 2 ** 31:
+            raise ValueError("vocabulary and new vertices together exceed the int32 tokens of the kernels")
+        # token -> vocabulary index, n_vocab + new index, or -1
+        index = torch.cat([vocab.index_of[seen[known]].long(), n_vocab + torch.arange(n_new, device=dev)])
+        keys, order = torch.sort(torch.cat([seen[known], new_ids]))
+        index = index[order]
+        at = torch.searchsorted(keys, walks.clamp(min=0)).clamp(max=max(keys.numel() - 1, 0))
+        idx = torch.where(walks >= 0, index[at], torch.full_like(walks, -1)).to(torch.int32)
+        idx = sgns.split_rows(idx)
+        syn1neg = self.model._syn1neg
+        syn1neg = syn1neg if isinstance(syn1neg, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(syn1neg))
+        sample_int = sgns.make_sample_int(vocab.counts, float(p["sample"] or 0.0))
+        frozen = SimpleNamespace(syn0=wv._device_vectors(), syn1neg=syn1neg.to(device=dev, dtype=torch.float32),
+                                 cum_table=sgns.make_cum_table(vocab.counts, float(p["ns_exponent"])).to(dev),
+                                 cum_index=None, sample_int=None if sample_int is None else sample_int.to(dev),
+                                 exp_table=torch.from_numpy(sgns.exp_table()).to(dev), window=int(p["window"]),
+                                 negative=int(p["negative"]), seed=int(p["seed"]))
+        rows, _ = foldin.fold_in(frozen, idx, n_new, int(p["iter"]) if epochs is None else int(epochs),
+                                 float(p["alpha"]), float(p["min_alpha"]), init=init)
+        column, who = self._who(new_ids.cpu().numpy())
+        return pd.DataFrame({column: who, "vector": corpus.list_column(rows.cpu().numpy(), "list")})
 
     # -- results ------------------------------------------------------------------
     def iter_embedding(self, chunk_rows: int = 1 << 18, vector_column: str = "auto"):
@@ -1052,6 +1132,11 @@ class Node2VecSpark(Node2VecBase, _ModelQueries):
             return pd.DataFrame({"word": np.array([], np.int64), "vector": []})
         word = int(wv.ids[row]) if wv.ids is not None else int(wv.index2word[row])
         return pd.DataFrame({"word": np.array([word], np.int64), "vector": [wv.rows(row, row + 1)[0].tolist()]})
+
+    def infer_vertices(self, df_walks_or_tensor, epochs: Optional[int] = None, init=None):
+        """Not available: fold-in (Node2VecHIP.infer_vertices) is defined for skip-gram negative sampling; the
+        pairs of hierarchical softmax are trained against tree nodes, another definition."""
+        raise ValueError("infer_vertices is defined for skip-gram negative sampling only (Node2VecHIP, sg=1)")
 
     def save_model(self, cloud_path: str, model_name: str) -> None:
         """embedding.py:276-285: "<path>/<name>.sparkml", a directory"""
