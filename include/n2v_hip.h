@@ -1265,6 +1265,27 @@ int n2v_foldin_train(const n2v_foldin_record *records, const int64_t *vertex_off
                      int32_t walk_len, float *new_rows, const float *syn1neg, const uint32_t *cum_table,
                      const float *exp_table, const n2v_sgns_params *params_host, void *stream);
 
+/* UMAP layouts of 2-D points (csrc/n2v_umap.hip, DESIGN.md "UMAP").  ADDITIONS ONLY: N2V_ABI_VERSION stays 15.
+ * One epoch: rowptr int64 [n + 1], col int32 [nnz] ascending within a row, eps fp32 [nnz] (the epochs per sample,
+ * w_max / w) are a symmetric CSR; Y, Y_next: row-major fp32 [n, 2], 8-byte aligned, Y_next a buffer other than Y.
+ * Entry t fires in epoch e iff eps[t] is finite and >= 1 and floorf((float)(e + 1) / eps[t]) > floorf((float)e /
+ * eps[t]); an entry whose column is outside [0, n) never fires; a row's range is clamped to [0, nnz).  Row i is one
+ * sequential chain from y = Y[i] over its firing entries t ascending: two attractions towards Y[col[t]], then
+ * `negative` repulsions from Y[k], k = ((mix64(ht ^ ((s + 1) * 0x8CB92BA72F3D8DD7)) >> 32) * n) >> 32 for s ascending
+ * (k == i skipped), ht = mix64(he + (t + 1) * 0xD1B54A32D192ED03), he = mix64(seed ^ mix64(epoch +
+ * 0x9E3779B97F4A7C15)); every other point is read from Y; Y_next[i] = y.  The fp32 operations of the two moves are
+ * spelled at the top of csrc/n2v_umap.hip and restated in tests/cpu_umap/n2v_umap_cpu.c: the result is a function of
+ * the arguments alone, bit for bit, whatever max_blocks (> 0: at most that many blocks; 0: a block per 256 rows).
+ * No float atomics.  N2V_EINVAL before any launch: n outside [0, 2^31), nnz < 0, negative outside [0, 64], epoch
+ * outside [0, 2^31 - 1), max_blocks < 0, a or b not finite and positive, gamma or alpha not finite; then (n > 0) a
+ * NULL or misaligned pointer or Y_next == Y.  n == 0 is N2V_OK and launches nothing. */
+int n2v_umap_epoch(const int64_t *rowptr, const int32_t *col, const float *eps, int64_t nnz, const float *Y,
+                   float *Y_next, int64_t n, int32_t epoch, float a, float b, float gamma, float alpha,
+                   int32_t negative, uint64_t seed, int32_t max_blocks, void *stream);
+/* out[i] = the epoch's x[i]^b for x[i] > 0 (b == 1: x[i] itself; otherwise the spelled sequence of csrc/n2v_powb.h),
+ * 0 for any other x[i].  N2V_EINVAL: n outside [0, 2^40), b not finite and positive, (n > 0) a NULL pointer. */
+int n2v_umap_powb(const float *x, int64_t n, float b, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -508,6 +508,16 @@ class KeyedVectors:
         X, inv_norm = self._window(restrict_vocab, True)
         return tsne.fit(X, perplexity=perplexity, inv_norm=inv_norm, **kw)
 
+    def umap(self, n_neighbors: int = 15, restrict_vocab: Optional[int] = None, **kw):
+        """the UMAP layout of the vectors on the GPU (node2vec_amd.umap.fit, whose other arguments pass through): a
+        UMAPResult whose embedding[i] is the 2-D point of token index2word[i].  The neighbours are cosine over the
+        cached init_sims norms.  An epoch costs O(n n_neighbors): this is the map for vocabularies past t-SNE's
+        reach.  restrict_vocab fits only the first rows."""
+        from node2vec_amd import umap
+
+        X, inv_norm = self._window(restrict_vocab, True)
+        return umap.fit(X, n_neighbors=n_neighbors, inv_norm=inv_norm, **kw)
+
     def with_rows(self, tokens, rows) -> "KeyedVectors":
         """A new KeyedVectors holding this one's rows followed by `rows` [m, dim] under `tokens` (m vertex ids or
         strings: the vertices Node2VecHIP.infer_vertices folded in), so that most_similar, build_index, kmeans and
@@ -585,7 +595,7 @@ def _check_objective(p: Dict[str, Any]) -> None:
 
 class _ModelQueries:
     """The queries of a fitted model that Node2VecHIP and Node2VecSpark share: link_scores() / edge_embedding(),
-    link_classifier() / link_classifier_scores(), cluster() / silhouette(), classify(), project() and tsne().  They
+    link_classifier() / link_classifier_scores(), cluster() / silhouette(), classify(), project(), tsne() and umap().  They
     answer per vertex in vocabulary order, under ["id"], or ["name"] through name_id: a repeated id keeps its last
     name, and an id of the vocabulary that name_id does not list is a KeyError -- raised before any GPU work."""
 
@@ -600,6 +610,7 @@ class _ModelQueries:
     label_f1 = None
     pca_result = None
     tsne_result = None
+    umap_result = None
 
     def _wv(self) -> KeyedVectors:
         if self.model is None:
@@ -758,6 +769,16 @@ class _ModelQueries:
         column, who = self._who(self._vocab_ids(wv))  # the whole vocabulary, whatever restrict_vocab leaves
         self.tsne_result = wv.tsne(**kw)
         coords = self.tsne_result.embedding.cpu().numpy()
+        return pd.DataFrame({column: who[:coords.shape[0]], "x0": coords[:, 0], "x1": coords[:, 1]})
+
+    def umap(self, **kw) -> pd.DataFrame:
+        """["id" | "name", "x0", "x1"]: every vocabulary vertex on the UMAP layout of the vectors, in vocabulary order
+        (model.wv.umap, whose arguments pass through).  Names go through name_id as in project().  The UMAPResult
+        is kept as self.umap_result."""
+        wv = self._wv()
+        column, who = self._who(self._vocab_ids(wv))  # the whole vocabulary, whatever restrict_vocab leaves
+        self.umap_result = wv.umap(**kw)
+        coords = self.umap_result.embedding.cpu().numpy()
         return pd.DataFrame({column: who[:coords.shape[0]], "x0": coords[:, 0], "x1": coords[:, 1]})
 
 
