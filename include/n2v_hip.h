@@ -1286,6 +1286,44 @@ int n2v_umap_epoch(const int64_t *rowptr, const int32_t *col, const float *eps, 
  * 0 for any other x[i].  N2V_EINVAL: n outside [0, 2^40), b not finite and positive, (n > 0) a NULL pointer. */
 int n2v_umap_powb(const float *x, int64_t n, float b, float *out, void *stream);
 
+/* DBSCAN of trained vectors (csrc/n2v_dbscan.hip, DESIGN.md "Density clustering").  ADDITIONS ONLY: N2V_ABI_VERSION
+ * stays 15.  X, inv_norm and metric as for n2v_kmeans_*; 0 <= n < 2^31.  Rows i and j are WITHIN EPS when, in fp32
+ * with one rounding per spelled operation and dot(i, j) the chain of n2v_silhouette,
+ *   N2V_KMEANS_EUCLIDEAN  fmaxf(fmaf(-2, dot, xn_i + xn_j), 0) <= eps * eps   (xn: the row's sum of squares)
+ *   N2V_KMEANS_COSINE     1 - dot * (inv_norm[i] * inv_norm[j]) <= eps
+ * a test that is symmetric in (i, j) bit for bit; a row is always within eps of itself (added by index, not
+ * computed).  The canonical result: row i is core when counts[i] = #{j within eps of i, i included} >= min_samples;
+ * a cluster is a connected component of the core rows, numbered by its lowest core row; a row that is not core takes
+ * the lowest-numbered cluster with a core row within eps of it, or -1.  It depends on the set of pairs alone: the
+ * integer atomics that carry it cannot show, and max_blocks (> 0: at most that many blocks a scan; 0: what the device
+ * holds at once, twice over) never changes a value.  Nothing of size n x n is stored.  The rows should be finite
+ * (fmaxf drops a NaN: a Euclidean pair with a non-finite row counts as within eps).  The three calls are three scans
+ * over (tile of columns x chunk of rows); the lists are device memory: an entry outside [0, n) is skipped, never
+ * dereferenced.  N2V_EINVAL before any launch: sizes or metric out of range, cosine without inv_norm, eps negative
+ * or not finite, min_samples < 1, max_blocks < 0, a list length outside [0, n]; then (n > 0) a NULL required pointer,
+ * a workspace that is NULL, not 16-byte aligned or smaller than n2v_dbscan_workspace_bytes.  n == 0 is N2V_OK and
+ * launches nothing. */
+
+/* Bytes of workspace of each of the three calls (-1 for sizes they refuse, 0 for n == 0): the scan's columns padded
+ * to [round_up(n, 64)][round_up(dim, 16)] fp32 and fp32 [n] squared norms (each part rounded up to 256 bytes). */
+int64_t n2v_dbscan_workspace_bytes(int64_t n, int32_t dim);
+/* Scan 1, every row against every row: counts_out int32 [n]; core_out uint8 [n] (counts >= min_samples) or NULL. */
+int n2v_dbscan_count(const float *X, const float *inv_norm, int64_t n, int32_t dim, int32_t metric, float eps,
+                     int32_t min_samples, int32_t *counts_out, uint8_t *core_out, void *workspace,
+                     int64_t workspace_bytes, int32_t max_blocks, void *stream);
+/* Scan 2, core rows against core rows (pairs on or above the diagonal of the list): core int32 [n_core], the core
+ * rows; root_out int32 [n]: for a core row the lowest core row of its connected component (a lock-free union-find,
+ * csrc/n2v_unionfind.h, then flattened), for any other row its own index. */
+int n2v_dbscan_union(const float *X, const float *inv_norm, int64_t n, int32_t dim, int32_t metric, float eps,
+                     const int32_t *core, int64_t n_core, int32_t *root_out, void *workspace,
+                     int64_t workspace_bytes, int32_t max_blocks, void *stream);
+/* Scan 3, rows that are not core against core rows: labels int32 [n] holds the cluster id of every core row and -1
+ * elsewhere; labels[b] of every row b of border int32 [n_border] becomes the smallest labels[c] over the rows c of
+ * core within eps of b (unchanged when there is none).  n_core == 0 or n_border == 0 is N2V_OK. */
+int n2v_dbscan_border(const float *X, const float *inv_norm, int64_t n, int32_t dim, int32_t metric, float eps,
+                      const int32_t *core, int64_t n_core, const int32_t *border, int64_t n_border, int32_t *labels,
+                      void *workspace, int64_t workspace_bytes, int32_t max_blocks, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,7 +44,8 @@ SYMBOLS = ("n2v_abi_version", "n2v_status_string", "n2v_device_count", "n2v_alia
            "n2v_tsne_workspace_bytes", "n2v_tsne_repulse", "n2v_tsne_step", "n2v_ivfpq_workspace_bytes",
            "n2v_ivfpq_plan", "n2v_ivfpq_lut", "n2v_ivfpq_topk", "n2v_link_rank_workspace_bytes",
            "n2v_link_rank_plan", "n2v_link_rank", "n2v_foldin_pair_counts", "n2v_foldin_pair_records",
-           "n2v_foldin_train", "n2v_umap_epoch", "n2v_umap_powb")
+           "n2v_foldin_train", "n2v_umap_epoch", "n2v_umap_powb", "n2v_dbscan_workspace_bytes", "n2v_dbscan_count",
+           "n2v_dbscan_union", "n2v_dbscan_border")
 
 
 class WeightedHubs(C.Structure):
@@ -366,6 +367,18 @@ def load():
                                  C.c_int32, C.c_void_p]
     L.n2v_umap_powb.restype = C.c_int
     L.n2v_umap_powb.argtypes = [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
+    L.n2v_dbscan_workspace_bytes.restype = C.c_int64
+    L.n2v_dbscan_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+    L.n2v_dbscan_count.restype = C.c_int
+    L.n2v_dbscan_count.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    L.n2v_dbscan_union.restype = C.c_int
+    L.n2v_dbscan_union.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
+                                   C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    L.n2v_dbscan_border.restype = C.c_int
+    L.n2v_dbscan_border.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
+                                    C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                    C.c_void_p]
     _lib = L
     return L
 

@@ -13,6 +13,9 @@ silhouette_samples / silhouette_score (csrc/n2v_silhouette.hip; DESIGN.md "Clust
 clustering is, which inertia cannot: every distance of a scored row to every other row, on the GPU, in one fixed
 order as well.
 
+dbscan / neighbor_counts (csrc/n2v_dbscan.hip; DESIGN.md "Density clustering") are the density clustering: no k to
+choose, clusters of any shape, stray rows left as noise, and scikit-learn's labels exactly.
+
 Device tensors in and out.  There is no CPU path: a missing GPU or library raises.
 """
 from typing import NamedTuple, Optional, Tuple
@@ -44,6 +47,14 @@ class SilhouetteResult(NamedTuple):
     b: torch.Tensor        # fp64 [m]: the smallest mean distance to the rows of another cluster
     nearest: torch.Tensor  # int32 [m]: that cluster, -1: none
     counts: torch.Tensor   # int64 [k]: rows per cluster
+
+
+class DBSCANResult(NamedTuple):
+    labels: torch.Tensor     # int32 [n]: the cluster of every row, -1: noise
+    core_mask: torch.Tensor  # bool [n]: counts >= min_samples
+    n_clusters: int
+    counts: torch.Tensor     # int32 [n]: rows within eps of the row, itself included
+    sizes: torch.Tensor      # int64 [n_clusters]: rows per cluster
 
 
 def check_metric(metric: str) -> None:
@@ -334,3 +345,95 @@ def silhouette_score(X: torch.Tensor, labels, metric: str = "euclidean", sample_
     res = silhouette_samples(X, labels, metric, k, rows, inv_norm)
     s = res.s if rows is not None else res.s[member.to(res.s.device)]
     return float(s.mean())
+
+
+def _eps(eps) -> float:
+    """eps as the kernels take it: rounded to fp32, finite and >= 0"""
+    with np.errstate(over="ignore"):
+        eps = float(np.float32(eps))
+    if not (np.isfinite(eps) and eps >= 0.0):
+        raise ValueError(f"eps = {eps} must be finite and >= 0")
+    return eps
+
+
+def _finite(X: torch.Tensor) -> None:
+    if not bool(torch.isfinite(X).all()):
+        raise ValueError("X holds a value that is not finite")
+
+
+def _count(X, norms, eps, metric, min_samples, want_core, max_blocks):
+    """scan 1 -> (counts int32 [n], core bool [n] or None, the workspace for the scans that follow)"""
+    n, dim = X.shape
+    counts = torch.empty(n, dtype=torch.int32, device=X.device)
+    core = torch.empty(n, dtype=torch.uint8, device=X.device) if want_core else None
+    ws = _dense.workspace(_lib.load().n2v_dbscan_workspace_bytes, n, dim, device=X.device)
+    _lib.check(_lib.load().n2v_dbscan_count(X.data_ptr(), _dense.ptr(norms), n, dim, METRICS[metric], eps,
+                                            min_samples, counts.data_ptr(), _dense.ptr(core), ws.data_ptr(),
+                                            ws.numel(), max_blocks, _lib.current_stream_ptr()), "n2v_dbscan_count")
+    return counts, None if core is None else core.bool(), ws
+
+
+def neighbor_counts(X: torch.Tensor, eps: float, metric: str = "euclidean",
+                    inv_norm: Optional[torch.Tensor] = None, max_blocks: int = 0) -> torch.Tensor:
+    """int32 [n]: how many rows lie within eps of every row, itself included -- dbscan's first scan on its own,
+    for choosing eps (a row is core at min_samples <= its count).  Arguments as for dbscan."""
+    check_metric(metric)
+    eps = _eps(eps)
+    if int(max_blocks) < 0:
+        raise ValueError("max_blocks must be >= 0")
+    _dense.shape(X)
+    X = _dense.matrix(X)
+    _finite(X)
+    norms = _norms(X, metric, inv_norm)
+    with torch.cuda.device(X.device):
+        return _count(X, norms, eps, metric, 1, False, int(max_blocks))[0]
+
+
+def dbscan(X: torch.Tensor, eps: float, min_samples: int = 5, metric: str = "euclidean",
+           inv_norm: Optional[torch.Tensor] = None, max_blocks: int = 0) -> DBSCANResult:
+    """DBSCAN of the rows of X (csrc/n2v_dbscan.hip).  A row is core when at least min_samples rows, itself
+    included, lie within eps of it (Euclidean distance <= eps, or 1 - cosine <= eps; eps is rounded to fp32, and the
+    Euclidean test compares squared distances: there is no square root).  A cluster is a connected component of
+    core rows, numbered by its lowest core row; a row that is not core takes the lowest-numbered cluster with a core
+    row within eps of it, and is noise (-1) when there is none.  That is the labelling of
+    sklearn.cluster.DBSCAN(algorithm="brute"), label for label, wherever fp32 and fp64 agree on which pairs are
+    within eps.  The result depends on the set of those pairs alone: the same call gives the same labels whatever
+    the launch (max_blocks > 0 caps the blocks of a scan).  At most three scans of 2 n^2 dim FLOPs, the second over
+    the core rows and the third over (other rows x core rows); nothing of size n x n and no neighbour list is
+    stored.  Two host synchronisations (the sizes of the two row lists).  The rows must be finite.
+    silhouette_samples ignores labels outside [0, k), so result.labels goes straight into it (k = n_clusters):
+    noise rows are never counted and score NaN."""
+    check_metric(metric)
+    eps = _eps(eps)
+    if int(min_samples) != min_samples or int(min_samples) < 1:
+        raise ValueError(f"min_samples = {min_samples} must be an integer >= 1")
+    if int(max_blocks) < 0:
+        raise ValueError("max_blocks must be >= 0")
+    n, dim = _dense.shape(X)
+    X = _dense.matrix(X)
+    _finite(X)
+    norms = _norms(X, metric, inv_norm)
+    L = _lib.load()
+    min_samples, max_blocks = min(int(min_samples), (1 << 31) - 1), int(max_blocks)
+    with torch.cuda.device(X.device):
+        if n == 0:
+            none = torch.empty(0, dtype=torch.int32, device=X.device)
+            return DBSCANResult(none, none.bool(), 0, none.clone(), torch.zeros(0, dtype=torch.int64, device=X.device))
+        counts, core_mask, ws = _count(X, norms, eps, metric, min_samples, True, max_blocks)
+        core = torch.nonzero(core_mask)[:, 0].to(torch.int32)
+        root = torch.empty(n, dtype=torch.int32, device=X.device)
+        _lib.check(L.n2v_dbscan_union(X.data_ptr(), _dense.ptr(norms), n, dim, METRICS[metric], eps, core.data_ptr(),
+                                      core.numel(), root.data_ptr(), ws.data_ptr(), ws.numel(), max_blocks,
+                                      _lib.current_stream_ptr()), "n2v_dbscan_union")
+        # a cluster's id is the rank of its root among the roots: a mask and an exclusive sum
+        is_root = core_mask & (root == torch.arange(n, dtype=torch.int32, device=X.device))
+        rank = torch.cumsum(is_root, 0, dtype=torch.int32) - 1  # (at a root: the roots before it)
+        n_clusters = int(rank[-1]) + 1
+        labels = torch.where(core_mask, rank[root.long()], torch.full_like(rank, -1)).contiguous()
+        border = torch.nonzero(~core_mask)[:, 0].to(torch.int32)
+        _lib.check(L.n2v_dbscan_border(X.data_ptr(), _dense.ptr(norms), n, dim, METRICS[metric], eps,
+                                       core.data_ptr(), core.numel(), border.data_ptr(), border.numel(),
+                                       labels.data_ptr(), ws.data_ptr(), ws.numel(), max_blocks,
+                                       _lib.current_stream_ptr()), "n2v_dbscan_border")
+        sizes = torch.bincount(labels[labels >= 0].long(), minlength=n_clusters)
+    return DBSCANResult(labels, core_mask, n_clusters, counts, sizes)

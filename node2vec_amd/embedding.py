@@ -432,6 +432,18 @@ class KeyedVectors:
         X, inv_norm = self._window(restrict_vocab, metric == "cosine")
         return cluster.kmeans(X, k, metric=metric, inv_norm=inv_norm, **kw)
 
+    def dbscan(self, eps: float, min_samples: int = 5, metric: str = "cosine", restrict_vocab: Optional[int] = None,
+               **kw):
+        """DBSCAN of the vectors on the GPU (node2vec_amd.cluster.dbscan, whose other arguments pass through): a
+        DBSCANResult whose labels[i] is the cluster of row i (token index2word[i]), -1 for noise.  The default
+        metric is cosine (1 - cosine <= eps over the cached init_sims norms), as for kmeans; cluster.dbscan itself
+        defaults to "euclidean" as scikit-learn does.  restrict_vocab: only the first rows are clustered."""
+        from node2vec_amd import cluster
+
+        cluster.check_metric(metric)
+        X, inv_norm = self._window(restrict_vocab, metric == "cosine")
+        return cluster.dbscan(X, eps, min_samples, metric=metric, inv_norm=inv_norm, **kw)
+
     def silhouette(self, labels_or_result, metric: str = "cosine", restrict_vocab: Optional[int] = None, **kw):
         """the silhouette of every vector under a clustering, on the GPU (node2vec_amd.cluster.silhouette_samples,
         whose other arguments pass through): a SilhouetteResult.  labels_or_result: a label tensor (one per row,
@@ -611,6 +623,7 @@ class _ModelQueries:
     pca_result = None
     tsne_result = None
     umap_result = None
+    dbscan_result = None
 
     def _wv(self) -> KeyedVectors:
         if self.model is None:
@@ -711,6 +724,17 @@ class _ModelQueries:
         self.clusters = pd.DataFrame({column: who, "cluster": self.kmeans_result.labels.cpu().numpy()})
         self._cluster_metric = metric
         return self.clusters
+
+    def dbscan(self, eps: float, min_samples: int = 5, metric: str = "cosine", **kw) -> pd.DataFrame:
+        """["id" | "name", "cluster"]: the DBSCAN cluster of every vocabulary vertex, in vocabulary order, -1 for a
+        noise vertex (model.wv.dbscan, whose other arguments pass through).  The default metric is cosine, as in
+        cluster().  Names go through name_id as in cluster().  The DBSCANResult is kept as self.dbscan_result;
+        self.clusters and self.kmeans_result stay those of cluster()."""
+        wv = self._wv()
+        column, who = self._who(self._vocab_ids(wv))
+        self.dbscan_result = wv.dbscan(eps, min_samples, metric=metric, **kw)
+        labels = self.dbscan_result.labels.cpu().numpy()
+        return pd.DataFrame({column: who[:len(labels)], "cluster": labels})
 
     def silhouette(self) -> pd.DataFrame:
         """self.clusters plus a "silhouette" column: how well every vertex sits in the cluster cluster() gave it
